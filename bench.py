@@ -7,11 +7,19 @@ A "step" = one encode pass + one decode pass of the hot path over the whole batc
 (configs[1]: 65 536 streams, stride 1 / context map off = reference TestSimple), inputs resident in HBM.
 value = N * 65536 bytes * n_gpus / (t_enc + t_dec) in MB/s (10^6 B/s), whole job.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--config all|simple|mixing|decode_only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--config all|simple|mixing|decode_only] [--full] [--dump-outputs DIR]
 
-One JSON line.  `value` is always BASELINE configs[1]; at N = 1 the line also carries `configs.mixing` (configs[2]:
-context map + dynamic_context_mixing = 2) and `configs.decode_only` (configs[3]: pre-encoded random_then_unicode x 4096),
-each with its own bit-exactness flag, kernel times and roofline.
+One JSON line.  `value` is always BASELINE configs[1].  A plain run does what that figure needs: it builds the input, verifies the
+codec's first pass against the oracle, lets the table placement search finish, warms up, times K steps and prints the line.
+`--full` adds what takes runs of its own: at N = 1 the sub-records `configs.mixing` (configs[2]: context map +
+dynamic_context_mixing = 2), `configs.simple_binary` and `configs.decode_only` (configs[3]: pre-encoded random_then_unicode
+x 4096), each with its own bit-exactness flag, kernel times and roofline; the row-replay launches behind `roofline.replay_ms` /
+`request_*`; and the host-core `cpu_baseline` records.
+
+`--dump-outputs DIR` writes what the headline's last timed step computed (rank 0's streams) as float32 / float64 .npy files:
+`sizes` and `packed_offsets` of every stream, `packed_total`, and the coded bytes (`coded_sample`, concatenated) and decoded bytes
+(`decoded_sample`) of a fixed, seeded sample of streams.  The input depends only on the arguments, so two builds can be compared
+file by file.
 
 Multi-GPU: `--gpus N` with no WORLD_SIZE in the environment re-launches itself as N ranks under torch.distributed.run
 (one process per GPU, RCCL); under an external launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.  Rank 0 builds the
@@ -22,6 +30,7 @@ it, weak scaling), then the coded sizes are exchanged and the coded bytes gather
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -221,7 +230,8 @@ def spawn_ranks(args):
     port = 29400 + os.getpid() % 500
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a child process, not an exec: this one has initialised the HIP runtime (device_count above)
+    sys.exit(subprocess.call(cmd))
 
 
 def alloc_packed_outputs(torch, N, L, dev):
@@ -287,6 +297,31 @@ def verify_first_pass(torch, po, codec, ocfg, d_in, N, L, outs, d_back, n_check)
     return ok and bad == 0, len(picks)
 
 
+SEED = 20261016
+DUMP_DECODED_BYTES = 4 << 20       # decoded bytes in the sample (x 4 as float32); the coded sample is at most 1.125 x that
+
+
+def dump_outputs(torch, out_dir, outs, d_back, N, L):
+    """What a caller of the timed path receives after its last step, as .npy (float32 where exact, float64 for offsets): the coded
+    sizes and offsets of every stream (of a seeded sample of them beyond 2^20 streams), the packed total, and the coded and decoded
+    bytes of a seeded sample of streams (always the first and the last).  At most ~50 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    k = max(1, min(N, DUMP_DECODED_BYTES // L))
+    picks = np.unique(np.concatenate([[0, N - 1], rng.choice(N, size=k, replace=False)]))
+    every = np.arange(N) if N <= (1 << 20) else picks
+    sizes = outs["sizes"].cpu().numpy().astype(np.int64)
+    offs = outs["packed_offsets"].cpu().numpy()
+    coded = [outs["packed"][int(offs[i]):int(offs[i]) + int(sizes[i])].cpu().numpy() for i in picks]
+    arrays = {"sizes": sizes[every].astype(np.float32), "packed_offsets": offs[every].astype(np.float64),
+              "packed_total": outs["packed_total"].cpu().numpy().astype(np.float64),
+              "coded_sample": np.concatenate(coded).astype(np.float32),
+              "decoded_sample": d_back[torch.from_numpy(picks).to(d_back.device)].cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _order_record(codec):
     """the byte order the decoder's tables are laid out in (divans_gpu_codec_byte_order): mode, and the 12 most frequent byte values of a learned rank"""
     bo = codec.byte_order(with_rank=True)
@@ -308,8 +343,9 @@ def settle_placement(codec, step, limit=20):
     return extra
 
 
-def run_pair_config(torch, da, po, name, d_in, N, L, args, dev, barrier, world_note="", traffic_name=None, byte_order=None, steps=None, warmup=None):
-    """encode+decode config (simple or mixing): verify, time, report."""
+def run_pair_config(torch, da, po, name, d_in, N, L, args, dev, barrier, world_note="", traffic_name=None, byte_order=None, steps=None, warmup=None,
+                    dump_dir=None):
+    """encode+decode config (simple or mixing): verify, time, report (and with dump_dir, write the last timed step's outputs)."""
     cfg = da.config_simple() if name == "simple" else da.config_context_mixing()
     ocfg = po.config_simple() if name == "simple" else po.config_context_mixing()
     codec = da.LiteralCodec(cfg, L, device=dev.index)
@@ -348,6 +384,8 @@ def run_pair_config(torch, da, po, name, d_in, N, L, args, dev, barrier, world_n
         codec.encode_packed(d_in, N, L, outs["packed"], outs["packed_offsets"], outs["sizes"], outs["packed_total"])
     search_steps = settle_placement(codec, untimed_decode)    # the placement search ends before the warm-up: no timed step runs on a candidate
     elapsed, rec = timed_steps(torch, codec, d_in, N, L, outs, d_back, steps, warm, barrier)
+    if dump_dir:
+        dump_outputs(torch, dump_dir, outs, d_back, N, L)
     if not args.no_verify:   # the timed passes must have produced the same thing
         ok = ok and bool(torch.equal(outs["sizes"], first_sizes)) and bool(torch.equal(d_back, d_in)) and codec.status() == 0
     coded_total = int(outs["sizes"].to(torch.int64).sum().item())
@@ -357,11 +395,12 @@ def run_pair_config(torch, da, po, name, d_in, N, L, args, dev, barrier, world_n
             "pack_streams": avg(rec["pack"])}
     raw = N * L
     replay_ms = None
-    try:
-        codec.row_replay(d_in, N, L)                 # (first launch: untimed)
-        replay_ms = codec.row_replay(d_in, N, L)
-    except Exception as e:       # no replay instance for this configuration / cache organisation
-        sys.stderr.write(f"bench: row replay not available ({e})\n")
+    if args.full:
+        try:
+            codec.row_replay(d_in, N, L)                 # (first launch: untimed)
+            replay_ms = codec.row_replay(d_in, N, L)
+        except Exception as e:       # no replay instance for this configuration / cache organisation
+            sys.stderr.write(f"bench: row replay not available ({e})\n")
     # algorithmic bytes per launch: decode reads C + writes raw; the model pass reads raw and hands
     # 4 B per nibble to the rANS pass; the rANS pass reads that spill and writes C
     alg = {dk: raw + coded_total, "encode_model_pass": raw + 8 * raw, "encode_rans_pass": 8 * raw + coded_total,
@@ -431,11 +470,12 @@ def run_decode_only(torch, da, po, args, dev, copies=4096, steps=None):
     dk = codec.last_decode_kernel() or "lit_decode_kernel"
     kern = {dk: sum(kms) / len(kms)}
     replay_ms = None
-    try:
-        codec.row_replay(d_out, N, L, offsets=d_out_off, sizes=d_out_sz)
-        replay_ms = codec.row_replay(d_out, N, L, offsets=d_out_off, sizes=d_out_sz)
-    except Exception as e:
-        sys.stderr.write(f"bench: row replay not available ({e})\n")
+    if args.full:
+        try:
+            codec.row_replay(d_out, N, L, offsets=d_out_off, sizes=d_out_sz)
+            replay_ms = codec.row_replay(d_out, N, L, offsets=d_out_off, sizes=d_out_sz)
+        except Exception as e:
+            sys.stderr.write(f"bench: row replay not available ({e})\n")
     res = {
         "workload": f"BASELINE configs[3]: testdata/random_then_unicode ({data.size} B) as {nb} independent streams (4 x 65536 + {blocks[-1].size} B), coded once by the "
                     f"oracle under TestContextMixing options, x{copies} copies = {N} streams resident in HBM, decode only, every copy compared",
@@ -475,11 +515,18 @@ def main():
     ap.add_argument("--host-data", action="store_true", help="build the input with tests/workload.py on the host instead of on the GPU (same bytes; "
                     "keeps the tens of thousands of small torch kernels of the GPU generator out of profiler runs)")
     ap.add_argument("--input-cache", default="", help="with --host-data: directory that keeps the generated blocks between runs (profiler passes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the host-core baselines")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--diag-data", choices=["corpus", "zeros", "random", "repeat1k"], default="corpus",
                     help="diagnostics only: 'zeros' touches two CDF rows per stream (cache-resident ceiling)")
+    ap.add_argument("--full", action="store_true", help="also the sub-records of --config all, the row-replay roofline fields and the host-core "
+                    "baselines (a plain run measures the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the headline's last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config not in ("all", "simple", "mixing"):
+        ap.error("--dump-outputs writes the headline's outputs: --config all, simple or mixing")
 
     env_world = int(os.environ.get("WORLD_SIZE", "0"))
     if args.gpus > 1 and env_world == 0:
@@ -539,7 +586,8 @@ def main():
     if args.diag_data == "zeros":
         d_in = torch.zeros((N, L), dtype=torch.uint8, device=dev)
     elif args.diag_data == "random":
-        d_in = torch.randint(0, 256, (N, L), dtype=torch.uint8, device=dev)
+        gen = torch.Generator(device=dev); gen.manual_seed(SEED + first)     # the same bytes from run to run
+        d_in = torch.randint(0, 256, (N, L), dtype=torch.uint8, device=dev, generator=gen)
     else:
         corpus_t = torch.from_numpy(corpus).to(dev)
         if world > 1:
@@ -582,10 +630,11 @@ def main():
     sub_steps = min(args.steps, 5)       # the sub-records time fewer steps than the headline's K and warm up once (their "steps" says how many;
     sub_warm = min(args.warmup, 1)       # the placement search's untimed decodes come before either)
 
-    def pair_record(name, d_in=d_in, traffic_name=None, byte_order=None, steps=None, warmup=None):
+    def pair_record(name, d_in=d_in, traffic_name=None, byte_order=None, steps=None, warmup=None, dump_dir=None):
         """One encode+decode configuration on every rank: verify, time (max over ranks), at world > 1 gather the coded streams
         to rank 0 and check them there.  Returns (record for rank 0, bit-exact on all ranks)."""
-        res, codec, outs = run_pair_config(torch, da, po, name, d_in, N, L, args, dev, barrier, traffic_name=traffic_name, byte_order=byte_order, steps=steps, warmup=warmup)
+        res, codec, outs = run_pair_config(torch, da, po, name, d_in, N, L, args, dev, barrier, traffic_name=traffic_name, byte_order=byte_order, steps=steps, warmup=warmup,
+                                           dump_dir=dump_dir)
         elapsed = sharding.max_over_ranks(res["elapsed"], dev)
         coded_all, ok_count = sharding.sum_over_ranks([res["coded_total"], int(res["ok"])], dev)
         ok_all = ok_count == world
@@ -639,7 +688,7 @@ def main():
     head_name = "simple" if args.config in ("all", "simple") else ("mixing" if args.config == "mixing" else None)
     line = None
     if head_name:
-        rec, ok_all = pair_record(head_name)
+        rec, ok_all = pair_record(head_name, dump_dir=(args.dump_outputs if rank == 0 else None))
         if rank == 0:
             cfg_tag = "BASELINE configs[1]" if head_name == "simple" else "BASELINE configs[2]"
             if strong:
@@ -672,7 +721,7 @@ def main():
                 print(json.dumps(line))
             sys.exit("bench: GPU output is NOT bit-exact / round-trip failed")
 
-    if args.config in ("all", "mixing", "decode_only", "simple_binary"):
+    if (args.config == "all" and args.full) or args.config in ("mixing", "decode_only", "simple_binary"):
         sub = {}
         if args.config == "all":
             # configs[2] on the same streams; at world > 1 this is configs[4]'s second option set, with its own scatter/gather record
@@ -706,7 +755,7 @@ def main():
             torch.cuda.empty_cache()
         if world == 1 and args.config in ("all", "decode_only"):
             sub["decode_only"] = run_decode_only(torch, da, po, args, dev, steps=sub_steps)
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 import lzma
                 with lzma.open(os.path.join(ROOT, "tests", "golden", "random_then_unicode.xz")) as f:
                     rtu = np.frombuffer(f.read(), dtype=np.uint8).copy()
@@ -728,7 +777,7 @@ def main():
             sys.exit(f"bench: sub-config {bad} is NOT bit-exact")
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and head_name:   # the host-core baseline is a single-GPU-run item
+        if args.full and not args.no_cpu_baseline and world == 1 and head_name:   # the host-core baseline is a single-GPU-run item
             line["cpu_baseline"] = cpu_baseline(head_name, workload, corpus, L)
         print(json.dumps(line))
     if world > 1:

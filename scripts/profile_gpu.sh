@@ -5,6 +5,7 @@ set -u
 TAG=${1:-r01}
 shift || true
 BENCH_ARGS=${@:-"--streams 32768 --steps 2 --warmup 1 --no-cpu-baseline --no-verify"}
+BENCH_ARGS="--full $BENCH_ARGS"     # every sub-record and the row replay in the trace
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT

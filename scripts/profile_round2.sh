@@ -11,7 +11,9 @@ run_config () {
   local CFG=$1; shift
   local FULL=$1; shift
   local ARGS="--config $CFG --steps 2 --warmup 1 --no-cpu-baseline --host-data --input-cache /tmp/divans_cache --check-streams 64 --table-candidates 1"
+  ARGS="--full $ARGS"        # the row-replay launches whose counters feed roofline.request_*
   local OUT=$REPO/gpurun_out/prof_$TAG/$CFG
+  PROF_DIR=$(dirname $OUT)
   mkdir -p $OUT
   echo "python bench.py $ARGS" > $OUT/cmd.txt
   if [ "${SKIP_TRACE:-0}" != "1" ]; then
@@ -63,6 +65,6 @@ run_config mixing 1
 run_config decode_only ${PROFILE_FULL_ALL:-0}
 if [ "${PROFILE_BINARY:-0}" = "1" ]; then run_config simple_binary ${PROFILE_FULL_ALL:-0}; fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-cd $REPO && python bench.py > gpurun_out/prof_$TAG/bench_line.json 2> gpurun_out/prof_$TAG/bench_line.err
-tail -c 600 gpurun_out/prof_$TAG/bench_line.json
+cd $REPO && python bench.py --full > $PROF_DIR/bench_line.json 2> $PROF_DIR/bench_line.err
+tail -c 600 $PROF_DIR/bench_line.json
 fi

@@ -3,5 +3,5 @@ for lib in "" gpurun_exp/libdivans_ransold.so "" gpurun_exp/libdivans_ransold.so
   DIVANS_HIP_LIBRARY=$lib python bench.py --config simple --no-cpu-baseline --table-candidates 1 --steps 4 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('lib=$lib', d['value'], 'bit_exact', d['bit_exact'], d['kernel_ms'])"
 done
-python bench.py --total-streams 16384 --no-cpu-baseline > gpurun_out/r05c_bench_16384.json 2>/dev/null; python -c "
-import json; d=json.load(open('gpurun_out/r05c_bench_16384.json')); print(d['value'], d['bit_exact'], d['kernel_ms']); [print(k, v['value'], v['bit_exact'], v['kernel_ms']) for k,v in d.get('configs',{}).items()]"
+python bench.py --full --total-streams 16384 --no-cpu-baseline 2>/dev/null | python -c "
+import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['bit_exact'], d['kernel_ms']); [print(k, v['value'], v['bit_exact'], v['kernel_ms']) for k,v in d.get('configs',{}).items()]"

@@ -7,7 +7,7 @@ OUT=gpurun_out/r06_pad_subgrid.txt
 for lib in "" gpurun_exp/libdivans_pad10.so gpurun_exp/libdivans_pad26.so gpurun_exp/libdivans_pad52.so ""; do
   for cfg in "--config decode_only" "--config simple --total-streams 16384" "--config mixing --total-streams 16384"; do
     echo "== library ${lib:-product} $cfg" >> $OUT
-    DIVANS_HIP_LIBRARY=$lib python bench.py $cfg --steps 3 --warmup 1 --no-cpu-baseline --table-candidates 1 --check-streams 64 2>/dev/null | python -c "
+    DIVANS_HIP_LIBRARY=$lib python bench.py --full $cfg --steps 3 --warmup 1 --no-cpu-baseline --table-candidates 1 --check-streams 64 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 recs=[d] if d.get('value') else []

@@ -6,7 +6,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_r06/simple_binary
 mkdir -p $OUT /tmp/divans_cache
 cd /tmp && export TMPDIR=/tmp
-ARGS="--config simple_binary --steps 2 --warmup 1 --no-cpu-baseline --host-data --check-streams 64 --table-candidates 1"
+ARGS="--full --config simple_binary --steps 2 --warmup 1 --no-cpu-baseline --host-data --check-streams 64 --table-candidates 1"
 echo "python bench.py $ARGS" > $OUT/cmd.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $REPO/bench.py $ARGS > $OUT/bench_traced.json 2> $OUT/trace.log
 find $OUT/trace -name '*kernel_stats*' -exec cp {} $OUT/kernel_stats.csv \;

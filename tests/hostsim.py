@@ -59,14 +59,17 @@ def build_fuzzer():
 
 def build_program(name, source, lang="c++", sanitize_main=True):
     """tests/c/_build/<name>: `source` (a caller of the per-stream C ABI) linked with the sanitized harness objects;
-    sanitize_main=False leaves the caller itself uninstrumented (the reference's c/example.c trips UBSan in its own vec_u8.h)."""
+    sanitize_main=False leaves the caller itself uninstrumented (the reference's c/example.c trips UBSan in its own vec_u8.h).
+    A `source` ending in .o is an object compiled elsewhere (oracle/Makefile's _ref/example_host.o) and is linked as it is."""
     exe = os.path.join(OUT, name)
     san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
     objs = _objects("san", san + ["-msse4.2"])
     if _newer(exe, objs + [source]):
-        obj = os.path.join(OUT, name + ".main.o")
-        cc = [CXX, "-std=c++14"] if lang == "c++" else [CC, "-Wno-unused-result"]
-        subprocess.run(cc + (san if sanitize_main else ["-O1", "-g"]) + ["-c", source, "-o", obj, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(source)], check=True)
+        obj = source
+        if not source.endswith(".o"):
+            obj = os.path.join(OUT, name + ".main.o")
+            cc = [CXX, "-std=c++14"] if lang == "c++" else [CC, "-Wno-unused-result"]
+            subprocess.run(cc + (san if sanitize_main else ["-O1", "-g"]) + ["-c", source, "-o", obj, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(source)], check=True)
         subprocess.run([CXX] + san + ["-o", exe, obj] + objs + ["-lpthread"], check=True)
     return exe
 

@@ -176,15 +176,15 @@ def test_c_harness_and_cpp_adaptors_under_sanitizers(tmp_path, corpus):
     assert coded.size == ref.size and (coded == ref).all()
 
 
-REF_C = "/root/reference/c"
+REF_EXAMPLE_OBJ = os.path.join(ROOT, "oracle", "_ref", "example_host.o")
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_C, "example.c")), reason="the reference tree is not mounted here")
+@pytest.mark.skipif(not os.path.exists(REF_EXAMPLE_OBJ), reason="oracle/_ref/example_host.o is built by __graft_entry__.build() only where the reference tree is present")
 @pytest.mark.parametrize("args,env", [([], {}), (["-l"], {}), (["-l", "-cm", "-m2", "-s1"], {}), (["-l", "-w12"], {"NO_MALLOC": "1"}), ([], {"RUST_MALLOC": "1"})])
 def test_reference_example_c_on_the_host_logic(args, env, tmp_path, corpus):
-    """the reference's own C harness (c/example.c, compiled verbatim from where it lies) over the harness objects: compress ->
+    """the reference's own C harness (c/example.c, compiled verbatim by oracle/Makefile `ref_example`) over the harness objects: compress ->
     decompress -> memcmp with its three allocators, under the sanitizers.  The GPU tier runs the same program against the product."""
-    exe = hostsim.build_program("ref_example", os.path.join(REF_C, "example.c"), lang="c", sanitize_main=False)
+    exe = hostsim.build_program("ref_example", REF_EXAMPLE_OBJ, lang="c", sanitize_main=False)
     e = dict(SAN_ENV, ASAN_OPTIONS="detect_leaks=0"); e.update(env)       # the harness does not free its own buffers
     r = _run([exe] + args, env=e, timeout=300)
     assert r.returncode == 0 and "reduced to" in r.stdout, (r.returncode, r.stdout, r.stderr[-3000:])

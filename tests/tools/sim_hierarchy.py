@@ -4,14 +4,15 @@ replayed against LDS row caches + one XCD's L2 + its share of the Infinity Cache
     python tests/tools/sim_hierarchy.py [--streams 3584] [--config plain|mixing|both] [--data text|binary] [--layouts 0,1,...]
 
 Writes the blocks (tests/workload.py: the benchmark's streams, or random_then_unicode for --data binary) and -- for the mixing
-configuration -- the fused context table (oracle luts, TestContextMixing: cm[i] = i & 63, UTF8) into /tmp, builds the simulator with
-gcc and runs the layouts in parallel.  VERDICT r05 item 1."""
+configuration -- the fused context table (oracle luts, TestContextMixing: cm[i] = i & 63, UTF8) into a private temporary directory,
+builds the simulator there with gcc and runs the layouts in parallel.  VERDICT r05 item 1."""
 import argparse
 import ctypes
 import lzma
 import os
 import subprocess
 import sys
+import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -73,21 +74,21 @@ def main():
     ap.add_argument("--extra", default="", help="space-separated key=value passed to every run")
     ap.add_argument("--jobs", type=int, default=6)
     a = ap.parse_args()
-    exe = "/tmp/sim_hierarchy"
-    subprocess.check_call(["gcc", "-O2", "-o", exe, os.path.join(ROOT, "tests/tools/sim_hierarchy.c")])
-    bpath = f"/tmp/sim_blocks_{a.data}_{a.streams}.bin"
-    if not os.path.exists(bpath):
+    with tempfile.TemporaryDirectory(prefix="sim_hierarchy_") as work:
+        exe = os.path.join(work, "sim_hierarchy")
+        subprocess.check_call(["gcc", "-O2", "-o", exe, os.path.join(ROOT, "tests/tools/sim_hierarchy.c")])
+        bpath = os.path.join(work, f"sim_blocks_{a.data}_{a.streams}.bin")
         blocks_file(bpath, a.streams, a.data)
-    cpath = "/tmp/sim_ctxf.bin"
-    ctxf_file(cpath)
-    runs = []
-    for cfg in (["plain", "mixing"] if a.config == "both" else [a.config]):
-        for lay in a.layouts.split(","):
-            cmd = [exe, bpath, str(a.streams), "65536", "1" if cfg == "mixing" else "0", lay, f"ctxf={cpath}"] + a.extra.split()
-            runs.append(cmd)
-    with ThreadPoolExecutor(a.jobs) as ex:
-        for out in ex.map(lambda c: subprocess.run(c, capture_output=True, text=True).stdout, runs):
-            print(out, flush=True)
+        cpath = os.path.join(work, "sim_ctxf.bin")
+        ctxf_file(cpath)
+        runs = []
+        for cfg in (["plain", "mixing"] if a.config == "both" else [a.config]):
+            for lay in a.layouts.split(","):
+                cmd = [exe, bpath, str(a.streams), "65536", "1" if cfg == "mixing" else "0", lay, f"ctxf={cpath}"] + a.extra.split()
+                runs.append(cmd)
+        with ThreadPoolExecutor(a.jobs) as ex:
+            for out in ex.map(lambda c: subprocess.run(c, capture_output=True, text=True).stdout, runs):
+                print(out, flush=True)
 
 
 if __name__ == "__main__":
