@@ -182,6 +182,7 @@ def load_library():
     L.divans_gpu_codec_status.argtypes = [vp, ctypes.POINTER(u32)]
     L.divans_gpu_lit_encode_packed.argtypes = [vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, vp, u32]
     L.divans_gpu_selftest_cdf_ops.argtypes = [vp, vp, u32, vp]
+    L.divans_gpu_selftest_cdf_ops_on.argtypes = [vp, u32, vp, u32, vp]
     L.divans_gpu_selftest_rans_pairs.argtypes = [vp, vp, u32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.divans_gpu_codec_set_block_types.argtypes = [vp, u32]
     L.divans_gpu_lit_encode_segments_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, u64, vp, vp]
@@ -230,7 +231,7 @@ def exported_symbols():
         "divans_gpu_codec_set_geometry", "divans_gpu_codec_set_split_cache", "divans_gpu_codec_tune_tables", "divans_gpu_codec_search_tables", "divans_gpu_codec_table_placement", "divans_gpu_table_memory", "divans_gpu_set_table_va_cap", "divans_gpu_trim", "divans_gpu_codec_set_decoder", "divans_gpu_experimental_decoders", "divans_gpu_codec_set_byte_order", "divans_gpu_codec_byte_order", "divans_gpu_codec_row_replay", "divans_gpu_codec_set_rans_split", "divans_gpu_codec_set_encode_path", "divans_gpu_codec_set_bucket_batch", "divans_gpu_lit_model_batch",
         "divans_gpu_selftest_division", "divans_gpu_speed_supported", "divans_gpu_speed_accepted", "divans_gpu_codec_status", "divans_gpu_codec_clear_status", "divans_gpu_codec_status_async", "divans_gpu_codec_last_decode_kernel", "divans_gpu_codec_set_stream_flags", "divans_gpu_codec_set_block_types",
         "divans_gpu_lit_encode_segments_batch", "divans_gpu_lit_decode_segments_batch",
-        "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_rans_pairs", "divans_gpu_lit_encode_batch_chunks",
+        "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_cdf_ops_on", "divans_gpu_selftest_rans_pairs", "divans_gpu_lit_encode_batch_chunks",
         "divans_gpu_lit_encode_host_pipelined", "divans_gpu_lit_decode_host_pipelined", "divans_gpu_host_alloc", "divans_gpu_host_free",
         "divans_gpu_lit_stream_begin", "divans_gpu_lit_stream_encode", "divans_gpu_lit_stream_finish",
         "divans_gpu_lit_stream_decode_begin", "divans_gpu_lit_stream_decode",
@@ -473,11 +474,16 @@ class LiteralCodec:
         _check(self._lib.divans_gpu_codec_status(self._h, ctypes.byref(st)), "divans_gpu_codec_status")
         return int(st.value)
 
-    def selftest_cdf_ops(self, ops):
-        """ops: (n, 4) uint32 script (include/divans_gpu.h) -> (n, 16) int32 records"""
+    def selftest_cdf_ops(self, ops, impl=None):
+        """ops: (n, 4) uint32 script (include/divans_gpu.h) -> (n, 16) int32 records; impl: which of the device's restatements
+        of the arithmetic runs it (None = divans_gpu_selftest_cdf_ops, i.e. implementation 0)"""
         ops = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1, 4)
         out = np.zeros((ops.shape[0], 16), dtype=np.int32)
-        _check(self._lib.divans_gpu_selftest_cdf_ops(self._h, ops.ctypes.data, ops.shape[0], out.ctypes.data), "divans_gpu_selftest_cdf_ops")
+        if impl is None:
+            _check(self._lib.divans_gpu_selftest_cdf_ops(self._h, ops.ctypes.data, ops.shape[0], out.ctypes.data), "divans_gpu_selftest_cdf_ops")
+        else:
+            _check(self._lib.divans_gpu_selftest_cdf_ops_on(self._h, int(impl), ops.ctypes.data, ops.shape[0], out.ctypes.data),
+                   "divans_gpu_selftest_cdf_ops_on")
         return out
 
     def selftest_rans_pairs(self, pairs):

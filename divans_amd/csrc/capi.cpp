@@ -1594,13 +1594,35 @@ extern "C" int divans_gpu_selftest_division(divans_gpu_codec* c, uint64_t* misma
 // Test entry points: the device primitives in isolation (tests/test_gpu_reference_unit_tests.py ports the reference's
 // own unit tests onto them).
 extern "C" int divans_gpu_selftest_cdf_ops(divans_gpu_codec* c, const uint32_t* ops, uint32_t n_ops, int32_t* out) {
+    return divans_gpu_selftest_cdf_ops_on(c, 0u, ops, n_ops, out);
+}
+
+// The same script on one of the device's restatements of the arithmetic: 0 = generation 1 (lit_kernels.hip), 1 = lit_decode2.hip,
+// 2 = the bucketed encoder passes (lit_bucket_dev.h + mix_nibble), 3 = lit_decode_t.hip.
+extern "C" int divans_gpu_selftest_cdf_ops_on(divans_gpu_codec* c, uint32_t impl, const uint32_t* ops, uint32_t n_ops, int32_t* out) {
     if (!c || !ops || !out || n_ops == 0) return fail(DIVANS_GPU_EINVAL, "null argument");
+    if (impl == 3u) {
+#if !DIVANS_WITH_EXPERIMENTAL_DECODERS
+        return fail(DIVANS_GPU_EINVAL, "implementation 3 (lit_decode_t.hip) exists in experiment builds only (DIVANS_WITH_EXPERIMENTAL_DECODERS=1 python divans_amd/build.py --force)");
+#endif
+    }
+    if (impl > 3u) return fail(DIVANS_GPU_EINVAL, "unknown implementation (0 = generation 1, 1 = lit_decode2, 2 = bucketed encoder, 3 = lit_decode_t)");
+    for (uint32_t k = 0; k < n_ops; ++k) {
+        if (impl == 2u && ops[4u * k] == 9u) return fail(DIVANS_GPU_EINVAL, "op 9 (decode step): the bucketed encoder has no decoder");
+    }
     HIP_TRY(hipSetDevice(c->device));
     uint32_t* d_ops = nullptr; int32_t* d_out = nullptr;
     HIP_TRY(hipMalloc(&d_ops, (size_t)n_ops * 16u));
     if (hipMalloc(&d_out, (size_t)n_ops * 64u) != hipSuccess) { (void)hipFree(d_ops); return fail(DIVANS_GPU_ENOMEM, "hipMalloc failed"); }
     hipError_t e = hipMemcpyAsync(d_ops, ops, (size_t)n_ops * 16u, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_selftest_cdf_ops(d_ops, n_ops, d_out, c->stream);
+    if (e == hipSuccess) {
+        if (impl == 0u) e = launch_selftest_cdf_ops(d_ops, n_ops, d_out, c->stream);
+        else if (impl == 1u) e = launch_selftest_cdf_ops2(d_ops, n_ops, d_out, c->stream);
+        else if (impl == 2u) e = launch_selftest_cdf_ops_bucket(d_ops, n_ops, d_out, c->stream);
+#if DIVANS_WITH_EXPERIMENTAL_DECODERS
+        else e = launch_selftest_cdf_ops_t(d_ops, n_ops, d_out, c->stream);
+#endif
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n_ops * 64u, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d_ops); (void)hipFree(d_out);

@@ -141,8 +141,7 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
     uint32_t* tab = lds32 + BK_TAB_DW;
     const uint32_t inc = (uint32_t)b.inc; const int lim = b.lim;
     for (uint32_t i = lane; i < 128u; i += 64u) {
-        const uint32_t sym = i >> 3, k = i & 7u;
-        tab[i] = (2u * k >= sym ? inc : 0u) | (2u * k + 1u >= sym ? inc << 16 : 0u);
+        tab[i] = bk_tab_entry(i, inc);
     }
     __syncthreads();
     const size_t pl = b.slot;
@@ -181,9 +180,8 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
         uint32_t* rowl = my + 8u * (1u + hi);                                                           \
         BkRow H = bk_read(my, tab, hi), L = bk_read(rowl, tab, lo);                                     \
         const u32x2 v = {bk_pack(H, hi), bk_pack(L, lo)};                                               \
-        H.w0 += H.a0; H.w1 += H.a1; L.w0 += L.a0; L.w1 += L.a1;   /* frequentist_cdf.rs:75-78 */        \
-        if ((int)(H.w1.w >> 16) >= lim) bk_renorm(H);                                                   \
-        if ((int)(L.w1.w >> 16) >= lim) bk_renorm(L);                                                   \
+        bk_add(H); bk_add(L);                                                                           \
+        bk_renorm_at(H, lim); bk_renorm_at(L, lim);                                                     \
         *(u32x4*)my = H.w0; *(u32x4*)(my + 4) = H.w1; *(u32x4*)rowl = L.w0; *(u32x4*)(rowl + 4) = L.w1; \
         PV = v;                                                                                         \
     }

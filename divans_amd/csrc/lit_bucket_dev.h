@@ -68,6 +68,15 @@ __device__ __forceinline__ void bk_renorm(BkRow& r) {                           
     r.w1 = t1 - ((t1 >> 2) & 0x3fff3fffu);
 }
 
+// frequentist_cdf.rs:74-85 on the packed row: the add of the symbol's increment row (bk_read fetched it from the table
+// bk_tab_entry fills), then the renormalisation once the NEW total has reached the speed's limit
+__device__ __forceinline__ uint32_t bk_tab_entry(uint32_t i, uint32_t inc) {    // dword k = i & 7 of symbol i >> 3: entries 2k and 2k + 1 take `inc` from the symbol up
+    const uint32_t sym = i >> 3, k = i & 7u;
+    return (2u * k >= sym ? inc : 0u) | (2u * k + 1u >= sym ? inc << 16 : 0u);
+}
+__device__ __forceinline__ void bk_add(BkRow& r) { r.w0 += r.a0; r.w1 += r.a1; }              // frequentist_cdf.rs:75-78
+__device__ __forceinline__ void bk_renorm_at(BkRow& r, int lim) { if ((int)(r.w1.w >> 16) >= lim) bk_renorm(r); }
+
 __device__ __forceinline__ void bk_store_quad(u32x4* p, u32x4 v) {     // 8-byte aligned is enough for a global store
     asm volatile("global_store_dwordx4 %0, %1, off" : : "v"(p), "v"(v) : "memory");
 }

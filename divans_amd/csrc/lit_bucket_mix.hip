@@ -149,9 +149,8 @@ __global__ __launch_bounds__(64) void mix_chain_kernel(const MixBucketBatch b) {
     const uint32_t inch = (uint32_t)(MODEL == 0 ? b.inc0 : b.inc3), incl = (uint32_t)(MODEL == 0 ? b.inc0 : b.inc2);   // literal.rs:320,354 / :242
     const int limh = MODEL == 0 ? b.lim0 : b.lim3, liml = MODEL == 0 ? b.lim0 : b.lim2;
     for (uint32_t i = lane; i < 128u; i += 64u) {
-        const uint32_t sym = i >> 3, k = i & 7u;
-        tabh[i] = (2u * k >= sym ? inch : 0u) | (2u * k + 1u >= sym ? inch << 16 : 0u);
-        tabl[i] = (2u * k >= sym ? incl : 0u) | (2u * k + 1u >= sym ? incl << 16 : 0u);
+        tabh[i] = bk_tab_entry(i, inch);
+        tabl[i] = bk_tab_entry(i, incl);
     }
     __syncthreads();
     const size_t pl = b.slot;
@@ -188,9 +187,8 @@ __global__ __launch_bounds__(64) void mix_chain_kernel(const MixBucketBatch b) {
         const u32x2 vx = {(uint32_t)H.chi | (hi ? (uint32_t)H.cprev << 16 : 0u),                        \
                           (uint32_t)L.chi | (lo ? (uint32_t)L.cprev << 16 : 0u)};                       \
         const uint32_t vt = (H.w1.w >> 16) | (L.w1.w & 0xffff0000u);                                    \
-        H.w0 += H.a0; H.w1 += H.a1; L.w0 += L.a0; L.w1 += L.a1;   /* frequentist_cdf.rs:75-78 */        \
-        if ((int)(H.w1.w >> 16) >= limh) bk_renorm(H);                                                  \
-        if ((int)(L.w1.w >> 16) >= liml) bk_renorm(L);                                                  \
+        bk_add(H); bk_add(L);                                                                           \
+        bk_renorm_at(H, limh); bk_renorm_at(L, liml);                                                   \
         *(u32x4*)rowh = H.w0; *(u32x4*)(rowh + 4) = H.w1; *(u32x4*)rowl = L.w0; *(u32x4*)(rowl + 4) = L.w1; \
         RX = vx; RT = vt;                                                                               \
     }
@@ -320,26 +318,30 @@ __global__ __launch_bounds__(64) void mix_chain_kernel(const MixBucketBatch b) {
 // 5. the Weights recursion: one lane per (stream, nibble half).  model_weights[1] belongs to the high nibbles and
 //    model_weights[0] to the low nibbles (literal.rs:230), so the two halves of a stream are independent.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t mix_nibble(Weights& w, uint32_t st_x, uint32_t st_max, uint32_t cm_x, uint32_t cm_max) {
+// entry 15 of the mixed row: both rows contribute their own total, so the two products are equal, rs = ro = (cmax * smax) >> sh, and
+// (rs * mix + rs * (2^15 - mix) + 1) >> 15 = rs whatever the weight -- the third average costs a multiply and a shift
+__device__ __forceinline__ int mix_total(int cmax, int smax) {
+    const uint32_t prod = __umul24((uint32_t)cmax, (uint32_t)smax);
+    int lz = __clz((int)prod);
+    lz = lz > 17 ? 17 : lz;
+    return (int)(prod >> (17 - lz));
+}
+
+// REC (the selftest interpreter): also hands back the two model frequencies the Weights update took, cm | stride << 16
+template <bool REC = false>
+__device__ __forceinline__ uint32_t mix_nibble(Weights& w, uint32_t st_x, uint32_t st_max, uint32_t cm_x, uint32_t cm_max, uint32_t* model_freqs = nullptr) {
     const int mix_rate = w.norm;
     const int cm_s = (int)(cm_x & 0xffffu), cm_p = (int)(cm_x >> 16), st_s = (int)(st_x & 0xffffu), st_p = (int)(st_x >> 16);
     const int cmax = (int)cm_max, smax = (int)st_max;
     const int p_s = average_rows(cm_s, st_s, cmax, smax, mix_rate);       // frequentist_cdf.rs:58-72, entry sym
     const int p_p = average_rows(cm_p, st_p, cmax, smax, mix_rate);       //   entry sym-1 (0 | 0 -> 0 when sym == 0)
-    // entry 15: both rows contribute their own total, so the two products are equal, rs = ro = (cmax * smax) >> sh, and
-    // (rs * mix + rs * (2^15 - mix) + 1) >> 15 = rs whatever the weight -- the third average costs a multiply and a shift
-    int pmax;
-    {
-        const uint32_t prod = __umul24((uint32_t)cmax, (uint32_t)smax);
-        int lz = __clz((int)prod);
-        lz = lz > 17 ? 17 : lz;
-        pmax = (int)(prod >> (17 - lz));
-    }
+    const int pmax = mix_total(cmax, smax);
     const float rp = biased_rcp15(pmax), rc = biased_rcp15(cmax), rs = biased_rcp15(smax);
     const uint32_t qp = scaled_div(p_p, pmax, rp);
     const uint32_t freq = scaled_div(p_s, pmax, rp) - qp - 1u;            // probability/interface.rs:97-108
     const uint32_t fcm = scaled_div(cm_s, cmax, rc) - scaled_div(cm_p, cmax, rc) - 1u;
     const uint32_t fst = scaled_div(st_s, smax, rs) - scaled_div(st_p, smax, rs) - 1u;
+    if (REC) *model_freqs = (fcm & 0xffffu) | (fst << 16);
     weights_update(w, (int)(short)fcm, (int)(short)fst, (int)(short)freq);   // literal.rs:236-239
     return (qp + 1u) | (freq << 16);
 }
@@ -437,6 +439,92 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     }
 #undef MW_FETCH
 #undef MW_STAGE
+}
+
+// The script interpreter of divans_gpu_selftest_cdf_ops_on (include/divans_gpu.h), implementation 2: the ops of
+// cdf_ops_selftest_kernel (lit_kernels.hip) on the bucketed encoder's arithmetic.  The two rows are 8 packed dwords each in LDS
+// and one lane walks them the way a lane of bucket_chain_kernel / mix_chain_kernel walks its bucket: bk_read, bk_pack, bk_add of
+// the increment row from a table filled by bk_tab_entry (refilled when the script's speed changes), bk_renorm_at, store; the
+// mixed step is mix_nibble on the records mix_chain_kernel's MX_POS forms.  The blend ops do not run bk_pack (ops 3 / 4 do), and op 2
+// averages all 16 entries with average_rows + mix_total although production only ever averages entries sym and sym-1.  The encoder has no symbol search: op 4 finds the
+// symbol with the reference's compare written out plainly and takes (start, freq) from bk_pack; op 9 is refused by the host.
+__global__ __launch_bounds__(64) void cdf_ops_selftest_bucket_kernel(const u32x4* ops, uint32_t n, int32_t* out) {
+    __shared__ __attribute__((aligned(16))) uint32_t rows[2][8];
+    __shared__ __attribute__((aligned(16))) uint32_t tab[128];
+    const uint32_t lane = threadIdx.x;
+    const u32x4 def0 = {4u | (8u << 16), 12u | (16u << 16), 20u | (24u << 16), 28u | (32u << 16)};
+    const u32x4 def1 = {36u | (40u << 16), 44u | (48u << 16), 52u | (56u << 16), 60u | (64u << 16)};
+    uint32_t tab_inc = 0u;
+    for (uint32_t i = lane; i < 128u; i += 64u) tab[i] = bk_tab_entry(i, tab_inc);
+    if (lane == 0u) for (uint32_t r = 0; r < 2u; ++r) { *(u32x4*)rows[r] = def0; *(u32x4*)(rows[r] + 4) = def1; }
+    __syncthreads();
+    Weights w; w.w0 = 1; w.w1 = 1; w.norm = 1 << 14;
+    for (uint32_t k = 0; k < n; ++k) {
+        const u32x4 op = ops[k];
+        const uint32_t kind = (uint32_t)__builtin_amdgcn_readfirstlane((int)op.x), sym = op.y & 15u;
+        const bool is_blend = kind == 0u || kind == 1u || kind == 7u;
+        if (is_blend && (uint32_t)__builtin_amdgcn_readfirstlane((int)op.z) != tab_inc) {
+            tab_inc = (uint32_t)__builtin_amdgcn_readfirstlane((int)op.z);
+            __syncthreads();
+            for (uint32_t i = lane; i < 128u; i += 64u) tab[i] = bk_tab_entry(i, tab_inc);
+            __syncthreads();
+        }
+        int32_t rec[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rec[i] = 0;
+        const uint16_t* r0 = (const uint16_t*)rows[0]; const uint16_t* r1 = (const uint16_t*)rows[1];
+        if (kind == 5u) weights_update(w, (int)(short)op.y, (int)(short)op.z, (int)(short)op.w);
+        if (kind == 6u) { w.w0 = 1; w.w1 = 1; w.norm = 1 << 14; }
+        if (kind == 8u && op.y >= 2u) { if (op.z == 0u) w.w0 = (int)op.w; else if (op.z == 1u) w.w1 = (int)op.w; else w.norm = (int)(op.w & 0xffffu); }
+        if (lane == 0u) {
+            if (is_blend) {
+                uint32_t* row = rows[kind == 1u];
+                BkRow R = bk_read(row, tab, sym);
+                bk_add(R);
+                bk_renorm_at(R, (int)op.w);
+                *(u32x4*)row = R.w0; *(u32x4*)(row + 4) = R.w1;
+                for (int i = 0; i < 16; ++i) rec[i] = ((const uint16_t*)row)[i];
+            } else if (kind == 2u) {
+                const int cmax = r0[15], smax = r1[15];
+                for (int i = 0; i < 15; ++i) rec[i] = average_rows(r0[i], r1[i], cmax, smax, (int)op.y);
+                rec[15] = mix_total(cmax, smax);
+            } else if (kind == 3u || kind == 4u) {
+                uint32_t s = sym;
+                if (kind == 4u) {       // probability/interface.rs:136-198: the first i < 15 with (slot * max >> 15) < cdf[i], else 15
+                    const int rescaled = (int)(((op.y & 0x7fffu) * (uint32_t)r0[15]) >> 15);
+                    s = 15u;
+                    for (uint32_t i = 0; i < 15u; ++i) if (rescaled < (int)r0[i]) { s = i; break; }
+                }
+                const BkRow R = bk_read(rows[0], tab, s);
+                const uint32_t sf = bk_pack(R, s);
+                rec[0] = (int)(sf & 0xffffu); rec[1] = (int)(sf >> 16); rec[2] = (int)s;
+            } else if (kind == 6u) {
+                for (uint32_t r = 0; r < 2u; ++r) { *(u32x4*)rows[r] = def0; *(u32x4*)(rows[r] + 4) = def1; }
+                for (int i = 0; i < 16; ++i) rec[i] = r0[i];
+            } else if (kind == 8u && op.y < 2u) {
+                ((uint16_t*)rows[op.y])[op.z & 15u] = (uint16_t)op.w;
+                for (int i = 0; i < 16; ++i) rec[i] = ((const uint16_t*)rows[op.y])[i];
+            } else if (kind == 10u) {   // the records of MX_POS (entry sym | entry sym-1 << 16, the row totals), then mix_weights_kernel's step
+                const BkRow C = bk_read(rows[0], tab, sym), S = bk_read(rows[1], tab, sym);
+                const uint32_t cm_x = (uint32_t)C.chi | (sym ? (uint32_t)C.cprev << 16 : 0u), st_x = (uint32_t)S.chi | (sym ? (uint32_t)S.cprev << 16 : 0u);
+                uint32_t mf = 0u;
+                const uint32_t sf = mix_nibble<true>(w, st_x, S.w1.w >> 16, cm_x, C.w1.w >> 16, &mf);
+                rec[0] = (int)(sf & 0xffffu); rec[1] = (int)(sf >> 16); rec[2] = (int)sym; rec[3] = (int)(mf & 0xffffu); rec[4] = (int)(mf >> 16);
+                rec[5] = w.w0; rec[6] = w.w1; rec[7] = w.norm;
+            }
+            if (kind == 5u || (kind == 8u && op.y >= 2u)) { rec[0] = w.w0; rec[1] = w.w1; rec[2] = w.norm; }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) out[(size_t)k * 16u + (uint32_t)i] = rec[i];
+        }
+        if (kind == 10u) {              // lane 0 ran the update: every lane keeps the same Weights
+            w.w0 = __builtin_amdgcn_readfirstlane(w.w0); w.w1 = __builtin_amdgcn_readfirstlane(w.w1); w.norm = __builtin_amdgcn_readfirstlane(w.norm);
+        }
+    }
+}
+
+hipError_t launch_selftest_cdf_ops_bucket(const uint32_t* d_ops, uint32_t n, int32_t* d_out, hipStream_t st) {
+    hipLaunchKernelGGL(cdf_ops_selftest_bucket_kernel, dim3(1), dim3(64), 0, st, (const u32x4*)d_ops, n, d_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_bucket_mix_model(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st) {

@@ -299,18 +299,26 @@ __device__ __forceinline__ int blend2(int c, int li1, bool above, int inc, int l
     return c;
 }
 
-// sym_to_start_and_freq for the searched symbol under the row `cv`, state update, blend and store: the non-mixing nibble
-template <bool PRESENT>
-__device__ __forceinline__ void finish2(const Table2& tb, const DmCache& dc, int li1, int rbase4, const RowSlot& slot_ref, int value,
-                                        bool is_default, int cv, const Searched& s, uint32_t slot, uint64_t& S, int inc, int lim) {
+// sym_to_start_and_freq (probability/interface.rs:97-108) for the searched symbol: the scaled entries sym and sym-1 of the row
+// `cv` -- one division pass on the numerator the search left (c15), then two ds_bpermute reads.  start = dpsym + 1,
+// freq = dsym - dpsym - 1.
+__device__ __forceinline__ void scaled_pair2(int cv, const Searched& s, int rbase4, uint32_t& dsym, uint32_t& dpsym) {
     const float rl = biased_rcp15(s.mx);
     const uint32_t q = (uint32_t)((float)cv * rl);
     const int32_t r = s.c15 - __mul24((int)q, s.mx);
     const uint32_t d = r >= s.mx ? q + 1u : q;
     const int dp = row_prev_or_zero((int)d);
     const int addr = rbase4 + (s.sym << 2);
-    const uint32_t dsym = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)d);
-    const uint32_t dpsym = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, dp);
+    dsym = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)d);
+    dpsym = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, dp);
+}
+
+// sym_to_start_and_freq for the searched symbol under the row `cv`, state update, blend and store: the non-mixing nibble
+template <bool PRESENT>
+__device__ __forceinline__ void finish2(const Table2& tb, const DmCache& dc, int li1, int rbase4, const RowSlot& slot_ref, int value,
+                                        bool is_default, int cv, const Searched& s, uint32_t slot, uint64_t& S, int inc, int lim) {
+    uint32_t dsym, dpsym;
+    scaled_pair2(cv, s, rbase4, dsym, dpsym);
     advance_state(S, slot, dsym, dpsym);
     int st = value;
     if (!is_default) st = blend2(st, li1, s.above, inc, lim, s.mx);     // cv == value here, so mx is its total and `above` its predicate
@@ -321,7 +329,12 @@ __device__ __forceinline__ void finish2(const Table2& tb, const DmCache& dc, int
 // stride row, each entry scaled by its own row total -- through ONE division pass: lanes 0/1 take p, lanes 4/5 the context-map
 // row, lanes 8/9 the stride row; even lanes entry sym, odd lanes entry sym-1 (lane 15 of the own row when sym == 0: its scaled
 // value is 2^15, which the 15-bit mask turns into the 0 the reference uses there).
-struct MixLanes { int addr_bias; bool is_p, is_cm, odd; };
+struct MixLanes {
+    int addr_bias; bool is_p, is_cm, odd;
+    // the selftest interpreter's copy of the assignment in decode2_body (which keeps its own line: going through this function
+    // moved one instruction in two of its mixing instances)
+    __device__ __forceinline__ void set(int li) { odd = (li & 1) != 0; is_p = li < 4; is_cm = (li & 12) == 4; addr_bias = odd ? -4 : 0; }
+};
 __device__ __forceinline__ uint32_t mixed_sf2(int p, int cm, int st, int pmax, int cmax, int smax, const MixLanes& ml, int rbase4, int sym,
                                               uint32_t& dprev_out, uint32_t& wfreqs) {
     const int a = rbase4 | (((sym << 2) + ml.addr_bias) & 60);
@@ -439,6 +452,7 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
     const uint32_t stream_base = lds_base + (threadIdx.x >> 4) * (b.cache_bytes_per_wg / (LIT_THREADS / 16));
     const Caches cc = make_caches<(CM & CM_2WAY) != 0>(b, stream_base, li);
     MixLanes ml;
+    // the same assignment as MixLanes::set (the selftest interpreter's copy): change both together
     ml.odd = (li & 1) != 0; ml.is_p = li < 4; ml.is_cm = (li & 12) == 4; ml.addr_bias = ml.odd ? -4 : 0;
     for (uint32_t s = gg; s < b.n_streams; s += G) {
         const uint32_t len = b.out_sizes ? b.out_sizes[s] : b.stream_len;
@@ -560,6 +574,92 @@ __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_kernel_any(const LitB
     decode2_body<MM, CTXC, MIX, SEG, CM>(b, lds);
 }
 
+
+// The script interpreter of divans_gpu_selftest_cdf_ops_on (include/divans_gpu.h), implementation 1: the ops of
+// cdf_ops_selftest_kernel (lit_kernels.hip) on THIS file's functions -- search2, scaled_pair2, advance_state, blend2 keyed by a
+// lane predicate (the search's own where a search ran, `lane >= sym` as replay_body has it otherwise), search_mix2, mixed_sf2, and
+// the Weights through WeightsPair::update with the same nibble in both halves.  Rows one entry per lane, as in decode2_body.
+__global__ __launch_bounds__(64) void cdf_ops_selftest2_kernel(const u32x4* ops, uint32_t n, int32_t* out) {
+    const int lane = threadIdx.x & 63, li = lane & 15, rbase = lane & 48, rbase4 = rbase << 2, li1 = li + 1;
+    int c0 = 4 * li1, c1 = 4 * li1;
+    WeightsPair wp; wp.init();
+    MixLanes ml; ml.set(li);
+    for (uint32_t k = 0; k < n; ++k) {
+        const u32x4 op = ops[k];
+        const int sym_in = (int)(op.y & 15u);
+        int rec = 0;
+        switch (op.x) {
+        case 0: case 7: c0 = blend2(c0, li1, li >= sym_in, (int)op.z, (int)op.w, row_bcast<15>(c0)); rec = c0; break;
+        case 1: c1 = blend2(c1, li1, li >= sym_in, (int)op.z, (int)op.w, row_bcast<15>(c1)); rec = c1; break;
+        case 2: rec = average_rows(c0, c1, row_bcast<15>(c0), row_bcast<15>(c1), (int)op.y); break;
+        case 3: case 4: {
+            Searched s;
+            if (op.x == 4u) s = search2(c0, op.y & 0x7fffu, rbase);
+            else { s.mx = row_bcast<15>(c0); s.c15 = c0 << 15; s.above = li >= sym_in; s.sym = sym_in; }
+            uint32_t d, dp;
+            scaled_pair2(c0, s, rbase4, d, dp);
+            rec = li == 0 ? (int)((dp + 1u) & 0xffffu) : (li == 1 ? (int)((d - dp - 1u) & 0xffffu) : (li == 2 ? s.sym : 0));
+            break;
+        }
+        case 5: {
+            const uint32_t fr = (op.y & 0xffffu) | (op.z << 16);
+            wp.update(li, fr, op.w, fr, op.w);
+            rec = li == 0 ? wp.w.w0 : (li == 1 ? wp.w.w1 : (li == 2 ? wp.w.norm : 0));
+            break;
+        }
+        case 6: c0 = 4 * li1; c1 = 4 * li1; wp.init(); rec = c0; break;
+        case 8:
+            if (op.y == 0u) { c0 = li == (int)(op.z & 15u) ? (int)(short)op.w : c0; rec = c0; }
+            else if (op.y == 1u) { c1 = li == (int)(op.z & 15u) ? (int)(short)op.w : c1; rec = c1; }
+            else {
+                if (op.z == 0u) wp.w.w0 = (int)op.w; else if (op.z == 1u) wp.w.w1 = (int)op.w; else wp.w.norm = (int)(op.w & 0xffffu);
+                rec = li == 0 ? wp.w.w0 : (li == 1 ? wp.w.w1 : (li == 2 ? wp.w.norm : 0));
+            }
+            break;
+        case 9: {                   // one nibble of decode2_body: plain (search2, finish2's pair, advance_state) or mixing (search_mix2, finish_mix2's)
+            uint64_t S = (uint64_t)op.y | ((uint64_t)op.z << 32);
+            uint32_t d, dp, wfreqs = 0u;
+            int sym;
+            if (op.w == 0u) {
+                const uint32_t slot = (uint32_t)S & 0x7fffu;
+                const Searched s = search2(c0, slot, rbase);
+                scaled_pair2(c0, s, rbase4, d, dp);
+                advance_state(S, slot, d, dp);
+                sym = s.sym;
+            } else {
+                MixRows r = {};
+                r.cm = c0; r.st = c1;
+                const MixSearched m = search_mix2(r, S, wp.norm_high(), rbase);
+                d = mixed_sf2(m.cv, r.cm, r.st, m.s.mx, m.cmax, m.smax, ml, rbase4, m.s.sym, dp, wfreqs);
+                advance_state(S, m.slot, d, dp);
+                sym = m.s.sym;
+            }
+            const int freq = (int)((d - dp - 1u) & 0xffffu);
+            rec = li == 0 ? (int)((dp + 1u) & 0xffffu) : (li == 1 ? freq : (li == 2 ? sym : (li == 3 ? (int)(uint32_t)S : (li == 4 ? (int)(uint32_t)(S >> 32) : 0))));
+            if (op.w != 0u) rec = li == 5 ? (int)(wfreqs & 0xffffu) : (li == 6 ? (int)(wfreqs >> 16) : (li == 7 ? freq : rec));
+            break;
+        }
+        case 10: {                  // the mixing nibble with the symbol given: mixed_sf2, then the byte loop's Weights update
+            const int cmax = row_bcast<15>(c0), smax = row_bcast<15>(c1);
+            const int cv = average_rows(c0, c1, cmax, smax, wp.norm_high());
+            uint32_t dp, wfreqs;
+            const uint32_t d = mixed_sf2(cv, c0, c1, row_bcast<15>(cv), cmax, smax, ml, rbase4, sym_in, dp, wfreqs);
+            const uint32_t pm = d - dp - 1u;
+            wp.update(li, wfreqs, pm, wfreqs, pm);
+            rec = li == 0 ? (int)((dp + 1u) & 0xffffu) : (li == 1 ? (int)(pm & 0xffffu) : (li == 2 ? sym_in : (li == 3 ? (int)(wfreqs & 0xffffu) : (li == 4 ? (int)(wfreqs >> 16) : 0))));
+            rec = li == 5 ? wp.w.w0 : (li == 6 ? wp.w.w1 : (li == 7 ? wp.w.norm : rec));
+            break;
+        }
+        default: break;
+        }
+        if (lane < 16) out[(size_t)k * 16u + (uint32_t)li] = rec;
+    }
+}
+
+hipError_t launch_selftest_cdf_ops2(const uint32_t* d_ops, uint32_t n, int32_t* d_out, hipStream_t st) {
+    hipLaunchKernelGGL(cdf_ops_selftest2_kernel, dim3(1), dim3(64), 0, st, (const u32x4*)d_ops, n, d_out);
+    return hipGetLastError();
+}
 
 // ---- the decoder's row traffic without the decoder (launch_row_replay, lit_kernels.h) ----
 // Same table layout, LDS caches, persistent grid and per-byte row selection as decode2_body for the stride-1 configurations (every

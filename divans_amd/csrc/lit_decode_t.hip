@@ -150,9 +150,10 @@ __device__ __forceinline__ void mix_search(MixT& m, const TRow& cm, const TRow& 
     m.sym = sym;
 }
 
-// the three (start, freq) pairs of the symbol, the state update, both blends and the Weights update (literal.rs:209-243, weights.rs:23-38)
-__device__ __forceinline__ void mix_finish(const MixT& m, TRow& cm, TRow& st, uint32_t pscr, uint64_t& S, Weights& w, bool is_default,
-                                           int inc_cm, int lim_cm, int inc_st, int lim_st) {
+// the scaled entries sym and sym-1 of the mixed row (d, dprev), the context-map row (dc, dcp) and the stride row (ds, dsp):
+// start = dprev + 1, freq = d - dprev - 1 (probability/interface.rs:97-108)
+__device__ __forceinline__ void mix_pairs(const MixT& m, const TRow& cm, const TRow& st, uint32_t pscr, uint32_t& d, uint32_t& dprev,
+                                          uint32_t& dc, uint32_t& dcp, uint32_t& ds, uint32_t& dsp) {
     u32x4 pa, pb;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { pa[j] = m.p[2 * j] | (m.p[2 * j + 1] << 16); pb[j] = m.p[8 + 2 * j] | (m.p[9 + 2 * j] << 16); }
@@ -164,9 +165,15 @@ __device__ __forceinline__ void mix_finish(const MixT& m, TRow& cm, TRow& st, ui
     const int ss = (int)lds_read16(st.addr + os), sp = (int)lds_read16(st.addr + op);
     const int pmax = (int)m.p[15];
     const float rp = biased_rcp15(pmax), rc = biased_rcp15((int)m.cmax), rs = biased_rcp15((int)m.smax);
-    const uint32_t d = scaled_div(ps, pmax, rp), dprev = nz ? scaled_div(pp, pmax, rp) : 0u;
-    const uint32_t dc = scaled_div(cs, (int)m.cmax, rc), dcp = nz ? scaled_div(cp, (int)m.cmax, rc) : 0u;
-    const uint32_t ds = scaled_div(ss, (int)m.smax, rs), dsp = nz ? scaled_div(sp, (int)m.smax, rs) : 0u;
+    d = scaled_div(ps, pmax, rp); dprev = nz ? scaled_div(pp, pmax, rp) : 0u;
+    dc = scaled_div(cs, (int)m.cmax, rc); dcp = nz ? scaled_div(cp, (int)m.cmax, rc) : 0u;
+    ds = scaled_div(ss, (int)m.smax, rs); dsp = nz ? scaled_div(sp, (int)m.smax, rs) : 0u;
+}
+// the three (start, freq) pairs of the symbol, the state update, both blends and the Weights update (literal.rs:209-243, weights.rs:23-38)
+__device__ __forceinline__ void mix_finish(const MixT& m, TRow& cm, TRow& st, uint32_t pscr, uint64_t& S, Weights& w, bool is_default,
+                                           int inc_cm, int lim_cm, int inc_st, int lim_st) {
+    uint32_t d, dprev, dc, dcp, ds, dsp;
+    mix_pairs(m, cm, st, pscr, d, dprev, dc, dcp, ds, dsp);
     advance_t(S, m.slot, d, dprev);
     uint32_t sel[8];
     blend_masks(m.sym, sel);
@@ -186,13 +193,17 @@ __device__ __forceinline__ uint32_t plain_search(const TRow& st, bool is_default
     for (int i = 0; i < 15; ++i) sym += (is_default ? 4u * (uint32_t)(i + 1) : entry(st, i)) <= th ? 1u : 0u;
     return sym;
 }
-__device__ __forceinline__ void plain_finish(TRow& st, bool is_default, uint32_t sym, uint32_t slot, uint32_t mx, uint64_t& S, int inc, int lim) {
+__device__ __forceinline__ void plain_pair(const TRow& st, bool is_default, uint32_t sym, uint32_t mx, uint32_t& d, uint32_t& dprev) {
     const uint32_t os = entry_off(sym), op = entry_off((sym - 1u) & 15u);
     const bool nz = sym != 0u;
     int xs = (int)lds_read16(st.addr + os), xp = (int)lds_read16(st.addr + op);
     if (is_default) { xs = 4 * (int)(sym + 1u); xp = 4 * (int)sym; }
     const float r = biased_rcp15((int)mx);
-    const uint32_t d = scaled_div(xs, (int)mx, r), dprev = nz ? scaled_div(xp, (int)mx, r) : 0u;
+    d = scaled_div(xs, (int)mx, r); dprev = nz ? scaled_div(xp, (int)mx, r) : 0u;
+}
+__device__ __forceinline__ void plain_finish(TRow& st, bool is_default, uint32_t sym, uint32_t slot, uint32_t mx, uint64_t& S, int inc, int lim) {
+    uint32_t d, dprev;
+    plain_pair(st, is_default, sym, mx, d, dprev);
     advance_t(S, slot, d, dprev);
     if (!is_default) {
         uint32_t sel[8];
@@ -426,6 +437,105 @@ uint32_t lit_lds_bytes_t(const LitBatch& b) {
 void lit_decode_t_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap) {
     const int mm = (b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4) ? b.geom.mm_uniform : -1;
     snprintf(buf, cap, "divans_hip::lit_decode_t_kernel<%d, %s, %s>", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false");
+}
+
+// The script interpreter of divans_gpu_selftest_cdf_ops_on (include/divans_gpu.h), implementation 3: the ops of
+// cdf_ops_selftest_kernel (lit_kernels.hip) on THIS file's functions -- blend_masks / blend_t / put_back, plain_search, plain_pair,
+// mix_search (its p[] is the averaged row), mix_pairs, advance_t, weights_update -- with the two rows as 8 packed dwords in
+// registers (TRow) and in a cache slot of the decoder's LDS layout (halves T_HALF apart; every lane works on its own copy, lane 0
+// reports).  Op 10 takes the average from mix_search and then installs the given symbol.
+__global__ __launch_bounds__(64) void cdf_ops_selftest_t_kernel(const u32x4* ops, uint32_t n, int32_t* out) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots[3u * T_SLOT];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)slots + lane * 16u;
+    const u32x4 def0 = {4u | (8u << 16), 12u | (16u << 16), 20u | (24u << 16), 28u | (32u << 16)};
+    const u32x4 def1 = {36u | (40u << 16), 44u | (48u << 16), 52u | (56u << 16), 60u | (64u << 16)};
+    TRow r0, r1;
+    r0.a = def0; r0.b = def1; r0.addr = base; r0.row = 0u; r0.fresh = false;
+    r1.a = def0; r1.b = def1; r1.addr = base + T_SLOT; r1.row = 1u; r1.fresh = false;
+    const uint32_t pscr = base + 2u * T_SLOT;
+    put_back(r0); put_back(r1);
+    Weights w; w.w0 = 1; w.w1 = 1; w.norm = 1 << 14;
+    for (uint32_t k = 0; k < n; ++k) {
+        const u32x4 op = ops[k];
+        const uint32_t kind = op.x, sym_in = op.y & 15u;
+        int32_t rec[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rec[i] = 0;
+        if (kind == 0u || kind == 1u || kind == 7u) {
+            TRow& r = kind == 1u ? r1 : r0;
+            uint32_t sel[8];
+            blend_masks(sym_in, sel);
+            blend_t(r, sel, (int)op.z, (int)op.w, r.b[3] >> 16);
+            put_back(r);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) rec[i] = (int)entry(r, i);
+        } else if (kind == 2u) {
+            MixT m;
+            mix_search(m, r0, r1, (int)op.y, 0ull);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) rec[i] = (int)m.p[i];
+        } else if (kind == 3u || kind == 4u) {
+            uint32_t slot, mx, d, dp;
+            uint32_t sym = plain_search(r0, false, (uint64_t)(op.y & 0x7fffu), slot, mx);
+            if (kind == 3u) sym = sym_in;
+            plain_pair(r0, false, sym, mx, d, dp);
+            rec[0] = (int)((dp + 1u) & 0xffffu); rec[1] = (int)((d - dp - 1u) & 0xffffu); rec[2] = (int)sym;
+        } else if (kind == 5u) {
+            weights_update(w, (int)(short)op.y, (int)(short)op.z, (int)(short)op.w);
+            rec[0] = w.w0; rec[1] = w.w1; rec[2] = w.norm;
+        } else if (kind == 6u) {
+            r0.a = def0; r0.b = def1; r1.a = def0; r1.b = def1;
+            put_back(r0); put_back(r1);
+            w.w0 = 1; w.w1 = 1; w.norm = 1 << 14;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) rec[i] = 4 * (i + 1);
+        } else if (kind == 8u) {
+            if (op.y < 2u) {
+                TRow& r = op.y == 1u ? r1 : r0;
+                lds_write16(r.addr + entry_off(op.z & 15u), op.w & 0xffffu);
+                r.a = lds_read128(r.addr); r.b = lds_read128(r.addr + T_HALF);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) rec[i] = (int)entry(r, i);
+            } else {
+                if (op.z == 0u) w.w0 = (int)op.w; else if (op.z == 1u) w.w1 = (int)op.w; else w.norm = (int)(op.w & 0xffffu);
+                rec[0] = w.w0; rec[1] = w.w1; rec[2] = w.norm;
+            }
+        } else if (kind == 9u && op.w == 0u) {
+            uint64_t S = (uint64_t)op.y | ((uint64_t)op.z << 32);
+            uint32_t slot, mx, d, dp;
+            const uint32_t sym = plain_search(r0, false, S, slot, mx);
+            plain_pair(r0, false, sym, mx, d, dp);
+            advance_t(S, slot, d, dp);
+            rec[0] = (int)((dp + 1u) & 0xffffu); rec[1] = (int)((d - dp - 1u) & 0xffffu); rec[2] = (int)sym;
+            rec[3] = (int)(uint32_t)S; rec[4] = (int)(uint32_t)(S >> 32);
+        } else if (kind == 9u || kind == 10u) {
+            uint64_t S = kind == 9u ? ((uint64_t)op.y | ((uint64_t)op.z << 32)) : 0ull;
+            MixT m;
+            mix_search(m, r0, r1, w.norm, S);
+            if (kind == 10u) m.sym = sym_in;
+            uint32_t d, dp, dc, dcp, ds, dsp;
+            mix_pairs(m, r0, r1, pscr, d, dp, dc, dcp, ds, dsp);
+            const int f = (int)((d - dp - 1u) & 0xffffu), fc = (int)((dc - dcp - 1u) & 0xffffu), fs = (int)((ds - dsp - 1u) & 0xffffu);
+            rec[0] = (int)((dp + 1u) & 0xffffu); rec[1] = f; rec[2] = (int)m.sym;
+            if (kind == 9u) {
+                advance_t(S, m.slot, d, dp);
+                rec[3] = (int)(uint32_t)S; rec[4] = (int)(uint32_t)(S >> 32); rec[5] = fc; rec[6] = fs; rec[7] = f;
+            } else {
+                weights_update(w, (int)(short)fc, (int)(short)fs, (int)(short)f);
+                rec[3] = fc; rec[4] = fs; rec[5] = w.w0; rec[6] = w.w1; rec[7] = w.norm;
+            }
+        }
+        if (lane == 0u) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) out[(size_t)k * 16u + (uint32_t)i] = rec[i];
+        }
+    }
+}
+
+hipError_t launch_selftest_cdf_ops_t(const uint32_t* d_ops, uint32_t n, int32_t* d_out, hipStream_t st) {
+    hipLaunchKernelGGL(cdf_ops_selftest_t_kernel, dim3(1), dim3(64), 0, st, (const u32x4*)d_ops, n, d_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_decode_t(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st) {

@@ -108,7 +108,9 @@ __device__ __forceinline__ void weights_update(Weights& w, int p_cm, int p_strid
     }
     const int error = (1 << 15) - pmix;
     const uint32_t geo = (uint32_t)__mul24(pmix, error);           // full_model_sum_p1 * full_model_sum_p0, below 2^28 (both factors below 2^16)
-    const int lg = geo ? 32 - __clz((int)geo) : 0;
+    // a negative pmix (two equal neighbours in the averaged row) makes the reference's i64 product negative: its bit length is 64
+    // and the release build's shift takes that amount mod 64, i.e. 0 -- the same as for a zero product
+    const int lg = (int)geo > 0 ? 32 - __clz((int)geo) : 0;
     const int n0 = new_weight(p_cm, pmix, error, lg, w.w0);
     const int n1 = new_weight(p_stride, pmix, error, lg, w.w1);
     w.w0 = n0; w.w1 = n1;

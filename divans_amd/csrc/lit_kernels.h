@@ -166,6 +166,7 @@ uint32_t lit_decode2_stream_lds(uint32_t dm_log2);   // LDS bytes one stream tak
 #if DIVANS_WITH_EXPERIMENTAL_DECODERS
 // lit_decode_t.hip: one lane per stream (decoder generation 4); 64 streams per workgroup
 hipError_t launch_decode_t(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st);
+hipError_t launch_selftest_cdf_ops_t(const uint32_t* d_ops, uint32_t n, int32_t* d_out, hipStream_t st);   // the selftest script on its arithmetic
 void lit_decode_t_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);
 uint32_t lit_decode_t_stream_lds(uint32_t dm_log2, bool mix);   // LDS bytes one stream takes there
 #endif
@@ -184,6 +185,9 @@ hipError_t launch_learn_byte_rank(const uint8_t* data, const uint64_t* offsets, 
 hipError_t launch_row_replay(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st);
 hipError_t launch_selftest_division(unsigned long long* d_mismatches, hipStream_t st);
 hipError_t launch_selftest_cdf_ops(const uint32_t* d_ops, uint32_t n, int32_t* d_out, hipStream_t st);
+// the same script on the arithmetic of lit_decode2.hip / of the bucketed encoder passes (lit_bucket_dev.h, lit_bucket_mix.hip)
+hipError_t launch_selftest_cdf_ops2(const uint32_t* d_ops, uint32_t n, int32_t* d_out, hipStream_t st);
+hipError_t launch_selftest_cdf_ops_bucket(const uint32_t* d_ops, uint32_t n, int32_t* d_out, hipStream_t st);
 
 }  // namespace divans_hip
 #endif

@@ -185,6 +185,11 @@ __device__ __forceinline__ bool wrap_scan(const LitGeometry& g, const Table<CACH
 // ---------------------------------------------------------------------------------------------
 // Encode, pass 1: adaptive model.  bytes -> (start | freq << 16) per nibble.
 // ---------------------------------------------------------------------------------------------
+// helper_advance_sym ans.rs:238: x = freq * (state >> 15) + (state & mask) - start (slot = the state's low 15 bits)
+__device__ __forceinline__ void advance_state1(uint64_t& S, uint32_t slot, uint32_t start, uint32_t freq) {
+    S = (uint64_t)freq * (S >> 15) + (uint64_t)slot - (uint64_t)start;
+}
+
 // Mixing paths: (start | freq << 16) of `sym` under the mixed row p, plus the frequencies of `sym` under the context-map row
 // and the stride row alone (wfreqs = cm freq | stride freq << 16, the Weights update's model_probs, literal.rs:236-239).
 // That is six quotients -- entries sym and sym-1 of three rows, each by its own row total (probability/interface.rs:97-108)
@@ -671,8 +676,7 @@ __device__ __forceinline__ uint32_t decode_nibble(const LitGeometry& g, const Ld
         packed = (uint32_t)row_gather((int)sf, rbase, sym);
     }
     const uint32_t start = packed & 0xffffu, freq = packed >> 16;
-    // helper_advance_sym ans.rs:238: x = freq * (state >> 15) + (state & mask) - start
-    S = (uint64_t)freq * (S >> 15) + (uint64_t)slot - (uint64_t)start;
+    advance_state1(S, slot, start, freq);
     if (MIX) {
         wpmix = freq;
         cm = blend_row_known_max(cm, li, sym, HIGH ? g.inc3 : g.inc2, HIGH ? g.lim3 : g.lim2, cmax, g.wrap_check != 0u);
@@ -705,7 +709,7 @@ __device__ __forceinline__ void finish_nibble(const LitGeometry& g, const Table<
     const uint32_t sf = (uint32_t)(dprev + 1) | ((uint32_t)((int)d - dprev - 1) << 16);
     const uint32_t packed = (uint32_t)row_gather((int)sf, rbase, sym);
     const uint32_t start = packed & 0xffffu, freq = packed >> 16;
-    S = (uint64_t)freq * (S >> 15) + (uint64_t)slot - (uint64_t)start;     // helper_advance_sym, ans.rs:238
+    advance_state1(S, slot, start, freq);
     int st = f.value;
     if (!f.is_default) st = blend_row_known_max(st, li, sym, g.inc0, g.lim0, mx, g.wrap_check != 0u);   // cv == f.value here, so mx is its total
     if (CACHE != 0 || !f.is_default) tb.store(f.ref, st);
@@ -893,6 +897,8 @@ __global__ void selftest_division_kernel(unsigned long long* mismatches) {
 // one entry per lane -- the GPU side of the reference's own CDF unit tests (probability/common_tests.rs:152-185
 // operation_test_helper compares two CDF implementations after every blend and at five mixing rates; here the second
 // implementation is the CPU restatement, compared on the host).  Every op writes one 16-entry record.
+// This is implementation 0 of divans_gpu_selftest_cdf_ops_on (include/divans_gpu.h lists the ops); lit_decode2.hip,
+// lit_bucket_mix.hip and (experiment builds) lit_decode_t.hip hold the interpreters of their own restatements of the arithmetic.
 __global__ __launch_bounds__(64) void cdf_ops_selftest_kernel(const u32x4* ops, uint32_t n, int32_t* out) {
     const int lane = threadIdx.x & 63, li = lane & 15, rbase = lane & 48;
     int c0 = 4 * (li + 1), c1 = 4 * (li + 1);
@@ -918,6 +924,43 @@ __global__ __launch_bounds__(64) void cdf_ops_selftest_kernel(const u32x4* ops, 
                 rec = li == 0 ? w.w0 : (li == 1 ? w.w1 : (li == 2 ? w.norm : 0)); break;
         case 6: c0 = 4 * (li + 1); c1 = 4 * (li + 1); w.w0 = 1; w.w1 = 1; w.norm = 1 << 14; rec = c0; break;
         case 7: c0 = blend_row_known_max(c0, li, (int)op.y, (int)op.z, (int)op.w, row_bcast<15>(c0)); rec = c0; break;   // the variant the pipelined paths use
+        case 8:                                                                                             // load an entry of a row / a field of the Weights
+            if (op.y == 0u) { c0 = li == (int)(op.z & 15u) ? (int)(short)op.w : c0; rec = c0; }
+            else if (op.y == 1u) { c1 = li == (int)(op.z & 15u) ? (int)(short)op.w : c1; rec = c1; }
+            else {
+                if (op.z == 0u) w.w0 = (int)op.w; else if (op.z == 1u) w.w1 = (int)op.w; else w.norm = (int)(op.w & 0xffffu);
+                rec = li == 0 ? w.w0 : (li == 1 ? w.w1 : (li == 2 ? w.norm : 0));
+            }
+            break;
+        case 9: case 10: {                                                                                  // one nibble of the decoder (lit_decode_kernel's steps) / of the mixing encoder
+            const bool mixed = op.x == 10u || op.w != 0u;
+            uint64_t S = (uint64_t)op.y | ((uint64_t)op.z << 32);
+            const uint32_t slot = (uint32_t)S & 0x7fffu;
+            const int cmax = row_bcast<15>(c0), smax = row_bcast<15>(c1);
+            const int cv = mixed ? average_rows(c0, c1, cmax, smax, w.norm) : c0;
+            const int mx = row_bcast<15>(cv);
+            const int sym = op.x == 10u ? (int)(op.y & 15u) : search_symbol(cv, slot, rbase);
+            uint32_t packed, wfreqs = 0u;
+            if (mixed) packed = mixed_start_freq(cv, c0, c1, mx, cmax, smax, li, rbase, sym, wfreqs);
+            else {
+                const uint32_t d = scaled_div(cv, mx, biased_rcp15(mx));
+                const int dprev = row_prev_or_zero((int)d);
+                const uint32_t sf = (uint32_t)(dprev + 1) | ((uint32_t)((int)d - dprev - 1) << 16);
+                packed = (uint32_t)row_gather((int)sf, rbase, sym);
+            }
+            const uint32_t start = packed & 0xffffu, freq = packed >> 16;
+            const int fcm = (int)(wfreqs & 0xffffu), fst = (int)(wfreqs >> 16);
+            rec = li == 0 ? (int)start : (li == 1 ? (int)freq : (li == 2 ? sym : 0));
+            if (op.x == 9u) {
+                advance_state1(S, slot, start, freq);
+                rec = li == 3 ? (int)(uint32_t)S : (li == 4 ? (int)(uint32_t)(S >> 32) : rec);
+                if (mixed) rec = li == 5 ? fcm : (li == 6 ? fst : (li == 7 ? (int)freq : rec));
+            } else {
+                weights_update(w, (int)(short)fcm, (int)(short)fst, (int)(short)freq);
+                rec = li == 3 ? fcm : (li == 4 ? fst : (li == 5 ? w.w0 : (li == 6 ? w.w1 : (li == 7 ? w.norm : rec))));
+            }
+            break;
+        }
         default: break;
         }
         if (lane < 16) out[(size_t)k * 16u + (uint32_t)li] = rec;

@@ -348,9 +348,20 @@ int divans_gpu_speed_accepted(int32_t inc, int32_t lim);
  *   16 x i32 record per operation in `out`:  0/1 blend row 0/1 (a = symbol, b = inc, c = lim) -> the row;
  *   2 row0.average(row1, a) -> the mixed row;  3 sym_to_start_and_freq(row0, a) / 4 cdf_offset_to_sym_start_and_freq(row0, a)
  *   -> {start, freq, sym};  5 Weights::update([a, b], c) -> {w0, w1, normalized_weight as u16};  6 reset;  7 = 0 through
- *   the blend variant of the pipelined paths.
+ *   the blend variant of the pipelined paths;
+ *   8 load: a = 0/1 sets entry b of row a to c -> the row; a = 2 sets field b of the Weights (0 = w0, 1 = w1, 2 = normalized_weight)
+ *   to c -> {w0, w1, normalized_weight as u16};  9 decode step: one nibble of the decoder from the rANS state a | b << 32 on row 0
+ *   (c = 0) or on row0.average(row1, rate of the Weights) (c = 1): search, start/freq, state step -> {start, freq, sym, new state
+ *   low half, high half} and, mixed, {.., freq of sym under row 0, under row 1, mixed freq} (rows and Weights unchanged);
+ *   10 mixed encode step of symbol a: start/freq under row0.average(row1, rate of the Weights), both model frequencies, then
+ *   Weights::update([freq under row 0, freq under row 1], mixed freq) -> {start, freq, sym, freq0, freq1, w0, w1, normalized_weight}.
+ *   start and freq are reported as u16.  Row 0 plays the context-map row, row 1 the stride row.
+ * cdf_ops_on runs the script on one of the device's restatements of that arithmetic: impl 0 = the generation-1 streaming kernels
+ *   (what cdf_ops runs), 1 = lit_decode2.hip, 2 = the bucketed encoder passes (packed rows of lit_bucket_dev.h + mix_nibble; it has
+ *   no decoder: EINVAL for op 9), 3 = lit_decode_t.hip (experiment builds; EINVAL otherwise).  Same script, same records.
  * rans_pairs: the LIFO rANS pass on n_pairs (even) caller-supplied (start | freq << 16) words of one stream. */
 int divans_gpu_selftest_cdf_ops(divans_gpu_codec *c, const uint32_t *ops, uint32_t n_ops, int32_t *out);
+int divans_gpu_selftest_cdf_ops_on(divans_gpu_codec *c, uint32_t impl, const uint32_t *ops, uint32_t n_ops, int32_t *out);
 int divans_gpu_selftest_rans_pairs(divans_gpu_codec *c, const uint32_t *pairs, uint32_t n_pairs, uint8_t *out, size_t cap, size_t *out_len);
 
 #ifdef __cplusplus

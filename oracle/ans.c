@@ -133,6 +133,11 @@ static void decoder_fill(orc_ans_decoder *d) {
     d->buffer_a_bytes_required = 0;
 }
 
+/* helper_advance_sym ans.rs:238: x = freq * (state >> 15) + (state & mask) - start, in wrapping u64 */
+uint64_t orc_ans_advance_state(uint64_t state, orc_prob start, orc_prob freq) {
+    return (uint64_t)(int64_t)freq * (state >> ORC_LOG2_SCALE) + (state & SCALE_MASK) - (uint64_t)(int64_t)start;
+}
+
 /* get_nibble_internal ans.rs:246-252 + helper_advance_sym :230-244 */
 uint8_t orc_ans_get_nibble(orc_ans_decoder *d, const orc_cdf16 *cdf, orc_sym_start_freq *coded) {
     decoder_fill(d);
@@ -141,7 +146,7 @@ uint8_t orc_ans_get_nibble(orc_ans_decoder *d, const orc_cdf16 *cdf, orc_sym_sta
     if (orc_cdf_offset_to_sym_start_and_freq(cdf, cdf_offset, &sf) != 0) { d->starved = 1; sf.start = 1; sf.freq = 1; sf.sym = 0; }
     d->buffer_a_bytes_required = d->buffer_b_bytes_required;
     d->buffer_a_bytes_required |= (uint8_t)((d->sym_count == (uint16_t)(ORC_ANS_NUM_SYMBOLS_BEFORE_FLUSH - 1)) << 3);
-    uint64_t x = (uint64_t)(int64_t)sf.freq * (d->state_a >> ORC_LOG2_SCALE) + (d->state_a & SCALE_MASK) - (uint64_t)(int64_t)sf.start;
+    uint64_t x = orc_ans_advance_state(d->state_a, sf.start, sf.freq);
     d->sym_count = (uint16_t)(d->sym_count + 1);
     d->buffer_b_bytes_required = (uint8_t)(x < NORMALIZATION_INTERVAL);
     d->state_a = d->state_b;

@@ -106,6 +106,12 @@ typedef struct {
 void orc_ans_decoder_init(orc_ans_decoder *d, const uint8_t *in, size_t in_len);
 /* fill (drain_or_fill_static_buffer for a decoder) + get_nibble, ans.rs:246-252,428-442 */
 uint8_t orc_ans_get_nibble(orc_ans_decoder *d, const orc_cdf16 *cdf, orc_sym_start_freq *coded);
+/* the state step of get_nibble alone, ans.rs:238 */
+uint64_t orc_ans_advance_state(uint64_t state, orc_prob start, orc_prob freq);
+
+/* ---- cdf_ops.c: the script the device selftest kernels run (include/divans_gpu.h, divans_gpu_selftest_cdf_ops_on), on the
+ *      functions above: ops = n x {kind, a, b, c} u32, out = n x 16 i32.  Returns 0, or -1 at an unknown op kind. ---- */
+int orc_cdf_ops_run(const uint32_t *ops, uint32_t n, int32_t *out);
 
 /* ---- literal coder configuration: what LiteralBookKeeping holds after the
  *      PredictionMode + BlockSwitchLiteral commands, codec/interface.rs:125-340 ---- */

@@ -142,7 +142,7 @@ class Weights:
         wi = weights[index]
         efficacy = i64(i64(total * n1i) - i64(p1 * ni))
         lg = 64 - lz64(i64(p1 * p0))
-        adj = i64(error * efficacy) >> lg if lg < 64 else (0 if i64(error * efficacy) >= 0 else -1)
+        adj = i64(error * efficacy) >> (lg & 63)             # i64 >> u32: a release build takes the amount mod 64 (lg == 64 when p1 * p0 is negative)
         return max(1, i32(i64(wi + adj)))
 
 

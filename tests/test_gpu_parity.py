@@ -363,6 +363,53 @@ def test_speeds_whose_total_stays_above_lim(mixing, encode_path, corpus, random_
         codec.close()
 
 
+EDGE_SPEEDS = [(8100, 16384), (8160, 1), (1, 16384), (2, 1024)]
+
+
+def edge_streams(corpus, shuffle384, L=65536):
+    """streams that bring rows to the edges of the CDF arithmetic through data: a row that sees one symbol only (all its mass on it,
+    total on the renormalisation cycle), two rows that alternate, a long run before / after text, every row touched equally, noise"""
+    text = corpus[5000:5000 + L]
+    return np.stack([np.zeros(L, np.uint8), np.full(L, 0xff, np.uint8), np.resize(np.array([0x0f, 0xf0], np.uint8), L),
+                     np.concatenate([np.full(40000, 0x41, np.uint8), text[:L - 40000]]),
+                     np.concatenate([text[:L - 40000], np.full(40000, 0x7a, np.uint8)]),
+                     np.resize(np.arange(256, dtype=np.uint8), L), np.random.default_rng(65536).integers(0, 256, L, dtype=np.uint8),
+                     np.resize(shuffle384, L)])
+
+
+@pytest.mark.parametrize("mixing", [0, 2])
+@pytest.mark.parametrize("encode_path", [1, 2])
+@pytest.mark.parametrize("rotate", [0, 2])
+def test_rows_kept_at_the_arithmetic_edges_by_data(mixing, encode_path, rotate, corpus, shuffle384):
+    # The primitive sweeps (test_gpu_cdf_ops_sweeps.py) do not see how a kernel KEEPS a row between nibbles (LDS caches, packed
+    # stores).  Here the data holds rows at the edges: totals that settle near 32 700 ((8100, 16384), (8160, 1): every update
+    # renormalises), a row that renormalises once in 16 320 updates ((1, 16384)), one that does every 480 ((2, 1024)), in each of the
+    # four adaptation slots (stride rows [0], SecondNibble [2], FirstNibble [3]), on 64 KiB streams that put all the mass on one symbol.
+    import divans_amd as da
+    speeds = EDGE_SPEEDS[rotate:] + EDGE_SPEEDS[:rotate]
+    for sp in EDGE_SPEEDS:
+        assert da.speed_supported(*sp)
+    rng = np.random.default_rng(4100 + mixing)
+    g, o = _random_config(rng, da, mixing, 0, [4], speeds)         # prediction mode 0, mixing value 4: the bucketed passes apply
+    blocks = edge_streams(corpus, shuffle384)
+    L = blocks.shape[1]
+    refs = [po.lit_encode(o, blocks[i]) for i in range(blocks.shape[0])]
+    for i, ref in enumerate(refs):                                  # the oracle's own round trip first: a failure here is about the oracle
+        assert (po.lit_decode(o, ref, L) == blocks[i]).all(), ("oracle round trip", speeds, i)
+    codec = da.LiteralCodec(g, L)
+    codec.set_encode_path(encode_path)
+    packed, offs, sizes = codec.encode_host(blocks, L)
+    assert codec.status() == 0
+    for i, ref in enumerate(refs):
+        got = packed[int(offs[i]):int(offs[i]) + int(sizes[i])]
+        assert got.size == ref.size and (got == ref).all(), (speeds, i, got.size, ref.size)
+    for gen in (2, 3):
+        codec.set_decoder(gen)
+        assert (codec.decode_host(packed, offs, sizes, L) == blocks).all(), (speeds, gen)
+        assert codec.status() == 0, (speeds, gen)
+    codec.close()
+
+
 @pytest.mark.parametrize("cfg_name", ["simple", "mixing"])
 @pytest.mark.parametrize("encode_path", [1, 2])
 @pytest.mark.parametrize("length", [1, 2, 63, 64, 65, 8191, 8192, 8193, 16385, 40000, 65535, 65536])

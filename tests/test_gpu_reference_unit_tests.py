@@ -7,6 +7,10 @@
 * common_tests.rs:3-126 `declare_common_tests!` -- start/freq chain identity, every 15-bit offset decodes to a monotone symbol
   inside its range, the LCG sample run (seed 1, common_tests.rs:44-48), repeated symbol 15 keeps all pdf > 0.
 * codec/weights.rs through Weights::update sequences (row a19 had no isolated GPU test).
+* Since the device holds several restatements of that arithmetic, every script runs on each of them (`impl`: the generation-1
+  streaming kernels, lit_decode2.hip, the bucketed encoder passes, in experiment builds lit_decode_t.hip) through divans_gpu_selftest_cdf_ops_on, against ONE table of
+  expected values: the oracle's C script interpreter (oracle/cdf_ops.c), which the Python restatement must match in full.
+  tests/test_gpu_cdf_ops_sweeps.py adds the edge-directed sweeps.
 * test_ans.rs:177-260 `encode_test_nibble_helper` for its five TestSelection variants: the model runs on the host (independent
   restatement), its (start, freq) pairs go through the GPU rANS pass alone, bytes compared with ANSEncoder's.
 """
@@ -16,6 +20,7 @@ import os
 import numpy as np
 import pytest
 
+import cdf_ops_sweeps as sw
 import pyoracle as po
 import ref_restatement as rr
 
@@ -35,60 +40,29 @@ def codec():
     c.close()
 
 
-class Mirror:
-    """the same script on the CPU restatements; returns the expected records"""
-    def __init__(self):
-        self.reset()
-
-    def reset(self):
-        self.c = [rr.Cdf(), rr.Cdf()]
-        self.o = [po.Cdf16(), po.Cdf16()]
-        for x in self.o:
-            po.lib().orc_cdf_default(ctypes.byref(x))
-        self.w = rr.Weights(); self.w.mixing_param = 2
-        self.ow = po.Weights(); po.lib().orc_weights_init(ctypes.byref(self.ow)); self.ow.mixing_param = 2
-
-    def run(self, ops):
-        L = po.lib()
-        out = np.zeros((len(ops), 16), dtype=np.int64)
-        for k, (kind, a, b, c) in enumerate(ops):
-            if kind in (0, 1, 7):
-                i = 1 if kind == 1 else 0
-                self.c[i].blend(a, (b, c)); L.orc_cdf_blend(ctypes.byref(self.o[i]), a, po.Speed(b, c))
-                assert list(self.o[i].cdf) == self.c[i].cdf
-                out[k] = self.c[i].cdf
-            elif kind == 2:
-                m = self.c[0].average(self.c[1], a)
-                om = po.Cdf16(); L.orc_cdf_average(ctypes.byref(self.o[0]), ctypes.byref(self.o[1]), a, ctypes.byref(om))
-                assert list(om.cdf) == m.cdf
-                out[k] = m.cdf
-            elif kind == 3:
-                s, f = self.c[0].sym_to_start_and_freq(a)
-                out[k, :3] = (s, f, a)
-            elif kind == 4:
-                sym, s, f = self.c[0].cdf_offset_to_sym_start_and_freq(a)
-                sf = po.SymStartFreq(); L.orc_cdf_offset_to_sym_start_and_freq(ctypes.byref(self.o[0]), a, ctypes.byref(sf))
-                assert (sf.sym, sf.start, sf.freq) == (sym, s, f)
-                out[k, :3] = (s, f, sym)
-            elif kind == 5:
-                self.w.update([a, b], c)
-                probs = (ctypes.c_int16 * 2)(a, b); L.orc_weights_update(ctypes.byref(self.ow), probs, c)
-                assert list(self.ow.model_weights) == self.w.model_weights and self.ow.normalized_weight == self.w.normalized_weight
-                out[k, :3] = (self.w.model_weights[0], self.w.model_weights[1], self.w.normalized_weight & 0xFFFF)
-            elif kind == 6:
-                self.reset(); out[k] = self.c[0].cdf
-        return out
+def implementations():
+    """the device's restatements of the CDF arithmetic this build can run a script on (include/divans_gpu.h,
+    divans_gpu_selftest_cdf_ops_on): generation 1, lit_decode2.hip, the bucketed encoder passes, and in experiment builds
+    lit_decode_t.hip"""
+    import divans_amd as da
+    return [0, 1, 2] + ([3] if da.experimental_decoders() else [])
 
 
-def run_both(codec, ops):
-    got = codec.selftest_cdf_ops(np.array(ops, dtype=np.uint32)).astype(np.int64)
-    exp = Mirror().run(ops)
-    bad = np.nonzero((got != exp).any(axis=1))[0]
-    assert bad.size == 0, (int(bad[0]), ops[int(bad[0])], got[bad[0]].tolist(), exp[bad[0]].tolist())
+IMPLS = implementations()
+
+
+def run_both(codec, impl, ops):
+    """the script on the device implementation `impl`; expected records from the C interpreter, which the Python restatement
+    (Mirror, itself checked call by call against the oracle's functions) must match in full"""
+    exp = sw.second_opinion(ops)
+    got = codec.selftest_cdf_ops(np.array(ops, dtype=np.uint32), impl).astype(np.int64)
+    sw.compare(impl, ops, got, exp, "reference unit test")
+    if impl == 0:       # divans_gpu_selftest_cdf_ops is implementation 0
+        assert (codec.selftest_cdf_ops(np.array(ops, dtype=np.uint32)).astype(np.int64) == got).all()
     return got
 
 
-def test_operation_test_helper_on_the_device_primitives(codec):
+def script_operation_test_helper():
     Q = 1 << 15
     ops = []
     for s in [3, 3, 9, 14, 0, 15, 7, 7, 7, 2] * 3:       # give row 1 a shape of its own (the reference leaves it at the default)
@@ -100,7 +74,13 @@ def test_operation_test_helper_on_the_device_primitives(codec):
         ops.append((7, s, *MED))                          # the pipelined kernels' blend variant must agree too
     for rate in (Q >> 2, Q >> 1, (Q >> 1) + (Q >> 2), 0, Q):
         ops.append((2, rate, 0, 0))
-    got = run_both(codec, ops)
+    return ops
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+def test_operation_test_helper_on_the_device_primitives(codec, impl):
+    ops = script_operation_test_helper()
+    got = run_both(codec, impl, ops)
     # assert_cdf_similar(average(.., all), cdf0) / (average(.., 0), cdf1): within max0*max1/160 after cross-scaling (common_tests.rs:128-150)
     r0, r1 = got[len(ops) - 6], got[29]
     for rec, ref in ((got[-1], r0), (got[-2], r1)):
@@ -108,22 +88,27 @@ def test_operation_test_helper_on_the_device_primitives(codec):
         assert all(abs(int(rec[i]) * m1 - int(ref[i]) * m0) < m0 * m1 // 160 for i in range(16))
 
 
-def test_declare_common_tests_invariants(codec):
+def script_declare_common_tests():
     ops = [(0, (i * 7 + 3) & 15, *MED) for i in range(100)]
     ops += [(3, s, 0, 0) for s in range(16)]
-    n_blend = len(ops)
     ops += [(4, off, 0, 0) for off in range(0, 1 << 15, 1)]
-    got = run_both(codec, ops)
+    return ops
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+def test_declare_common_tests_invariants(codec, impl):
+    ops = script_declare_common_tests()
+    got = run_both(codec, impl, ops)
     sf = got[100:116]
     for s in range(1, 16):                                 # common_tests.rs:14-17
         assert sf[s, 0] == 1 + sf[s - 1, 0] + sf[s - 1, 1]
-    dec = got[n_blend:]
+    dec = got[116:]
     assert (np.diff(dec[:, 2]) >= 0).all() and dec[0, 2] == 0 and dec[-1, 2] == 15     # monotone symbols, :29-39
     offs = np.arange(1 << 15)
     assert ((offs >= dec[:, 0] - 1) & (offs <= dec[:, 0] + dec[:, 1])).all()
 
 
-def test_lcg_sample_run_and_symbol_15_stress(codec):
+def script_lcg_sample_run():
     # simple_rand, common_tests.rs:44-48 (seed 1): x = x * 1103515245 + 12345; symbols drawn from a fixed pdf through a prefix table
     x = 1
     pdf = [0.1, 0.01, 0.03, 0.2, 0.02, 0.05, 0.04, 0.15, 0.01, 0.06, 0.03, 0.07, 0.02, 0.1, 0.08, 0.03]
@@ -134,12 +119,17 @@ def test_lcg_sample_run_and_symbol_15_stress(codec):
         u = ((x >> 16) & 0x7FFF) / 32768.0
         ops.append((0, int(np.searchsorted(edges, u, side="right").clip(0, 15)), *MED))
     ops += [(0, 15, *MED)] * 30000                         # common_tests.rs:94-103
-    got = run_both(codec, ops)
+    return ops
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+def test_lcg_sample_run_and_symbol_15_stress(codec, impl):
+    got = run_both(codec, impl, script_lcg_sample_run())
     final = got[-1]
     assert (np.diff(np.concatenate([[0], final])) > 0).all()      # every pdf entry still positive
 
 
-def test_weights_update_sequences(codec):
+def script_weights_update_sequences():
     rng = np.random.default_rng(7)
     ops = []
     for k in range(30000):
@@ -153,7 +143,25 @@ def test_weights_update_sequences(codec):
         else:
             p0 = p1 = pm = int(rng.integers(1, 32767))
         ops.append((5, p0, p1, pm))
-    run_both(codec, ops)
+    return ops
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+def test_weights_update_sequences(codec, impl):
+    run_both(codec, impl, script_weights_update_sequences())
+
+
+def test_what_an_implementation_lacks_is_refused(codec):
+    import divans_amd as da
+    if not da.experimental_decoders():
+        with pytest.raises(da.DivansGpuError, match="experiment builds"):
+            codec.selftest_cdf_ops(np.array([(6, 0, 0, 0)], dtype=np.uint32), 3)
+    else:
+        assert 3 in IMPLS
+    with pytest.raises(da.DivansGpuError, match="no decoder"):
+        codec.selftest_cdf_ops(np.array([(9, 1 << 31, 0, 0)], dtype=np.uint32), 2)
+    with pytest.raises(da.DivansGpuError, match="unknown implementation"):
+        codec.selftest_cdf_ops(np.array([(6, 0, 0, 0)], dtype=np.uint32), 4)
 
 
 # ---------------------------------------------------------------- test_ans.rs nibble helpers
