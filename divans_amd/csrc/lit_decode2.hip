@@ -552,6 +552,7 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
             // to exactly those; anything else means a truncated, corrupt or mismatched stream
             corrupt |= (SA != (1ull << 31)) | (SB != (1ull << 31));
         }
+        if (SEG && li == 0) sc.finish();
         corrupt |= ww.pos != ww.nwords;     // every coded word consumed, none read past the end
         if (corrupt && li == 0) {
             if (b.status) atomicOr(b.status, LIT_STATUS_BAD_STREAM);

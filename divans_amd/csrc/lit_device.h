@@ -246,6 +246,12 @@ struct SegCursor {
         segs = b.segs; idx = b.seg_begin[s]; end = b.seg_begin[s + 1]; left = 0u; status = b.status;
         advance(b.geom, last8, ctab);
     }
+    // After the stream's last byte, by one lane: the lengths have to add up to the stream.  A list that ends early leaves `left`
+    // wrapped below zero, one that goes on has bytes or segments over (trailing empty segments are consumed by advance() and
+    // do not count) -- either way bytes were coded under a context the caller did not mean, so say so.
+    __device__ __forceinline__ void finish() const {
+        if ((left != 0u || idx != end) && status) atomicOr(status, LIT_STATUS_BAD_SEGMENT);
+    }
 };
 
 }  // namespace divans_hip

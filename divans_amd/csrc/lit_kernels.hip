@@ -350,6 +350,7 @@ __global__ __launch_bounds__(LIT_THREADS) void lit_model_encode_kernel(const Lit
             mine = nxt;
             nxt = (base + 32u + li < len) ? in[base + 32u + li] : 0u;
         }
+        if (SEG && li == 0) sc.finish();
         if (MIX && b.wstate && (li & 7) == 0) {   // lanes 0 and 8 of the row hold the two Weights objects
             int32_t* p = b.wstate + (li ? 3 : 0);
             p[0] = wp.w.w0; p[1] = wp.w.w1; p[2] = wp.w.norm;
@@ -805,6 +806,7 @@ __global__ __launch_bounds__(LIT_THREADS) void lit_decode_kernel(const LitBatch 
             // NeedsMoreInput or fail its checksum)
             corrupt |= (SA != (1ull << 31)) | (SB != (1ull << 31));
         }
+        if (SEG && li == 0) sc.finish();
         if (b.consumed) { corrupt |= ww.pos > ww.nwords; if (li == 0) b.consumed[s] = ww.pos; }
         else corrupt |= ww.pos != ww.nwords;     // every coded word consumed, none read past the end
         if (MIX && b.wstate && (li & 7) == 0) {   // lanes 0 and 8 of the row hold the two Weights objects

@@ -102,7 +102,7 @@ int divans_gpu_lit_decode_batch(divans_gpu_codec *c, const uint8_t *d_in, const 
  * between Literal commands (src/codec/interface.rs:289-292), while the priors, the mixing Weights and the LIT rANS coder
  * run on: all literal bytes of the stream are ONE LIT_CODER byte stream.  One segment = one Literal command. */
 typedef struct divans_lit_segment {
-    uint32_t len;      /* literal bytes of this command (> 0) */
+    uint32_t len;      /* literal bytes of this command; 0 is allowed: such a segment codes nothing and the next one's context replaces its own */
     uint32_t btype;    /* literal block type in force (< the count given to divans_gpu_codec_set_block_types) */
     uint64_t last8;    /* the 8 output bytes before the command, oldest in bits 0..7, newest in bits 56..63 */
 } divans_lit_segment;
@@ -111,7 +111,10 @@ typedef struct divans_lit_segment {
  * the extra tables).  A segment naming a block type >= n_btypes raises DIVANS_GPU_STATUS_BAD_SEGMENT in the status word. */
 int divans_gpu_codec_set_block_types(divans_gpu_codec *c, uint32_t n_btypes);
 /* As divans_gpu_lit_encode_batch / _decode_batch; stream i's literal bytes (in command order, concatenated) are split
- * by the segments d_segs[d_seg_begin[i] .. d_seg_begin[i+1]) (device arrays; d_seg_begin has n_streams + 1 entries). */
+ * by the segments d_segs[d_seg_begin[i] .. d_seg_begin[i+1]) (device arrays; d_seg_begin has n_streams + 1 entries).
+ * The lengths of a stream's segments add up to its size (an empty stream has no segments or empty ones only): a list that
+ * covers fewer or more bytes raises DIVANS_GPU_STATUS_BAD_SEGMENT in the status word, in both directions -- the stream was
+ * coded under a context the list did not say; the other streams of the batch are not affected. */
 int divans_gpu_lit_encode_segments_batch(divans_gpu_codec *c, const uint8_t *d_in, const uint64_t *d_in_offsets,
                                          const uint32_t *d_in_sizes, uint32_t stream_len, uint32_t n_streams,
                                          const uint32_t *d_seg_begin, const divans_lit_segment *d_segs,
@@ -153,7 +156,8 @@ int divans_gpu_lit_stream_decode(divans_gpu_codec *c, const uint8_t *coded, size
  * The host-buffer wrappers check the same word themselves and return DIVANS_GPU_EINVAL / DIVANS_GPU_ECORRUPT. */
 #define DIVANS_GPU_STATUS_BAD_MODEL 1u
 #define DIVANS_GPU_STATUS_BAD_STREAM 2u
-#define DIVANS_GPU_STATUS_BAD_SEGMENT 4u   /* a segment's literal block type lies outside the tables divans_gpu_codec_set_block_types built */
+#define DIVANS_GPU_STATUS_BAD_SEGMENT 4u   /* a segment's literal block type lies outside the tables divans_gpu_codec_set_block_types built, or a
+                                              stream's segment lengths do not add up to its size */
 int divans_gpu_codec_status(divans_gpu_codec *c, uint32_t *status);
 /* Clears the word without waiting (stream-ordered, before the launches that follow): for callers that keep a codec across calls
  * and may have abandoned a launch sequence without reading its status. */
