@@ -14,18 +14,23 @@
 // The decoder cannot do this (it learns the bytes one at a time) and keeps the streaming kernels.
 #include "lit_bucket_dev.h"
 
+#ifndef DIVANS_BK_CHAIN_NO_STORES   // counterfactual: bucket_chain_kernel keeps its arithmetic and drops its pair stores (WRONG output: timing only)
+#define DIVANS_BK_CHAIN_NO_STORES 0
+#endif
+
 namespace divans_hip {
 
 // ---------------------------------------------------------------------------------------------
 // 1. per (stream, piece): sorted[slot] = byte, inv[pos] = slot, desc[stream][prev][piece] = start | count << 16
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const BucketBatch b) {
-    __shared__ __attribute__((aligned(16))) uint8_t staging[BK_PIECE];
+    __shared__ __attribute__((aligned(16))) unsigned long long staging64[BK_PIECE / 8u];   // lane masks while ranking, then the sorted bytes
+    uint8_t* staging = (uint8_t*)staging64;
     __shared__ __attribute__((aligned(16))) uint8_t piece_in[16 + BK_PIECE];   // piece_in[15] = the byte before the piece
     __shared__ uint32_t hist[4][256];
-    __shared__ uint32_t scan[256];
+    __shared__ uint32_t wsum[4];
     const uint32_t s = blockIdx.x / b.pieces, piece = blockIdx.x % b.pieces;
-    const uint32_t tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const uint32_t tid = threadIdx.x, w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63;
     const uint32_t len = b.in_sizes ? b.in_sizes[s] : b.stream_len;
     const uint8_t* in = b.in + (b.in_offsets ? b.in_offsets[s] : (uint64_t)s * b.stream_len);
     uint32_t* desc = b.desc + ((size_t)s * 256u + tid) * 8u + piece;
@@ -49,44 +54,59 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const Buck
     }
     __syncthreads();
     const uint8_t* key_of = piece_in + 15;      // key_of[p] = previous byte of position p, key_of[p + 1] = its own byte
-    // wave w owns positions [2048 w, 2048 w + 2048) of the piece and visits them in order, 64 at a time
+    // ONE ranking pass: wave w owns positions [2048 w, 2048 w + 2048) of the piece and visits them in order, 64 at a time.  The lanes
+    // that hold the same key find each other through the wave's 256 lane masks in LDS (in `staging`, which is free until placement):
+    // every lane clears its key's mask, ORs its own bit in and reads the mask back -- three LDS operations in program order, against the
+    // eight ballots with a 64-bit select per lane and bit that this walk used to cost.  The mask gives the position's rank among the 64
+    // positions' equal keys and the size of that key group; hist[w][key] holds the number of the wave's earlier positions with the key
+    // (the last lane of each key group adds the group's size: those lanes hold distinct keys, and a wave's LDS accesses stay in program
+    // order), so hist-before + rank is the position's rank among ALL of the wave's positions of its key: at most 2047, kept in
+    // registers, two per dword.
+    unsigned long long* mask_of = staging64 + w * 256u;     // relaxed atomics below: lanes meet in these words, nothing may be forwarded
+    const unsigned long long my_bit = 1ull << lane;
+    uint32_t kept[16];
+#pragma unroll
     for (uint32_t bt = 0; bt < 32u; ++bt) {
+        uint32_t r = 0;
         const uint32_t p = w * 2048u + bt * 64u + lane;
-        if (p < n) atomicAdd(&hist[w][key_of[p]], 1u);
+        if (p < n) {
+            const uint32_t key = key_of[p];
+            __hip_atomic_store(mask_of + key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_or(mask_of + key, my_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const unsigned long long same = __hip_atomic_load(mask_of + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const uint32_t rank = lanes_below(same), cnt = (uint32_t)__popcll(same);
+            const uint32_t before = hist[w][key];
+            r = before + rank;
+            if (rank == cnt - 1u) hist[w][key] = before + cnt;
+        }
+        if (bt & 1u) kept[bt >> 1] |= r << 16; else kept[bt >> 1] = r;
     }
     __syncthreads();
+    // the 256 totals' exclusive scan: each wave scans its 64 keys with shuffles, the four wave sums meet in LDS
     const uint32_t c0 = hist[0][tid], c1 = hist[1][tid], c2 = hist[2][tid], c3 = hist[3][tid];
     const uint32_t tot = c0 + c1 + c2 + c3;
-    scan[tid] = tot;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-        const uint32_t v = tid >= d ? scan[tid - d] : 0u;
-        __syncthreads();
-        scan[tid] += v;
-        __syncthreads();
+    uint32_t incl = tot;
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += v;
     }
-    const uint32_t start = scan[tid] - tot;
+    if (lane == 63u) wsum[w] = incl;
+    __syncthreads();
+    uint32_t start = incl - tot;
+    for (uint32_t j = 0; j < 3u; ++j) if (j < w) start += wsum[j];
     hist[0][tid] = start; hist[1][tid] = start + c0; hist[2][tid] = start + c0 + c1; hist[3][tid] = start + c0 + c1 + c2;
     *desc = start | (tot << 16);
     __syncthreads();
+    // placement: the slot is the key's base for this wave + the kept rank
     uint16_t* inv = b.inv + (size_t)s * pl + base;
+#pragma unroll
     for (uint32_t bt = 0; bt < 32u; ++bt) {
         const uint32_t p = w * 2048u + bt * 64u + lane;
-        const bool valid = p < n;
-        const uint32_t key = valid ? key_of[p] : 0u;
-        const uint32_t byte = valid ? key_of[p + 1u] : 0u;
-        unsigned long long same = __ballot(valid);
-        for (uint32_t bit = 0; bit < 8u; ++bit) {
-            const bool set = (key >> bit) & 1u;
-            const unsigned long long bb = __ballot(set);
-            same &= set ? bb : ~bb;
-        }
-        const uint32_t rank = lanes_below(same), cnt = (uint32_t)__popcll(same);
-        if (valid) {
-            const uint32_t off = hist[w][key];
-            staging[off + rank] = (uint8_t)byte;
-            inv[p] = (uint16_t)(off + rank);
-            if (rank == cnt - 1u) hist[w][key] = off + cnt;   // the wave's LDS accesses stay in program order
+        if (p < n) {
+            const uint32_t key = key_of[p], byte = key_of[p + 1u];
+            const uint32_t slot = hist[w][key] + ((kept[bt >> 1] >> (16u * (bt & 1u))) & 0xffffu);
+            staging[slot] = (uint8_t)byte;
+            inv[p] = (uint16_t)slot;
         }
     }
     __syncthreads();
@@ -189,7 +209,12 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
     for (;;) {
         u32x2 e = e_next; const uint32_t m = m_next;
         // 1. the previous group's pairs leave (their registers are free again below)
+#if DIVANS_BK_CHAIN_NO_STORES
+        asm volatile("" : : "v"(pv0), "v"(pv1), "v"(pv2), "v"(pv3), "v"(pv4), "v"(pv5), "v"(pv6), "v"(pv7), "v"(sfs_prev));
+        if (false) {
+#else
         if (m_prev & BK_VALID) {
+#endif
             u32x2* dst = sfs_prev + (m_prev & 0xffffu);
             const uint32_t pf = (m_prev >> 16) & 15u, pc = (m_prev >> 20) & 15u;
             if (pc == 8u) {
@@ -353,6 +378,10 @@ hipError_t launch_bucket_model(const BucketBatch& b, uint32_t chain_blocks, hipS
     }
     hipLaunchKernelGGL(bucket_sort_kernel, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
     hipLaunchKernelGGL(bucket_tasks_kernel, dim3((b.n_streams + 3u) / 4u), dim3(1024), 0, st, b);
+#if DIVANS_BK_CHAIN_NO_STORES   // every pair reads (start 1, freq 2048): the rANS pass stays inside its slots on the pairs nobody wrote
+    e = hipMemsetD32Async((hipDeviceptr_t)b.sfs, (int)(1u | (2048u << 16)), (size_t)b.n_streams * b.slot * 2u, st);
+    if (e != hipSuccess) return e;
+#endif
     hipLaunchKernelGGL(bucket_chain_kernel, dim3(chain_blocks), dim3(64), bucket_chain_lds_bytes(), st, b);
     hipLaunchKernelGGL(bucket_unsort_kernel, dim3(b.n_streams * b.pieces), dim3(1024), 0, st, b);
     return hipGetLastError();
