@@ -169,7 +169,8 @@ struct divans_gpu_codec {
     uint64_t* d_slot_off = nullptr; size_t slot_off_cap = 0;
     std::vector<hipEvent_t> ev_span; size_t enc_spans = 0;   // ... and its events: per sub-batch (start, before the pack, end)
     float last_pack_ms = 0;
-    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok), 1 streaming kernels, 2 bucketed
+    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
+    uint32_t last_encode_path = 0;   // the model pass of the last encode / model call: 1 streaming, 2 bucketed, 3 bucketed two-model (0: none yet)
     uint8_t* d_bk = nullptr;      size_t bk_bytes = 0; uint32_t bk_streams = 0;
     uint8_t* d_rs = nullptr;      size_t rs_bytes = 0;
     void* host_scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // device buffers of the host-buffer entry points, grow-only
@@ -764,6 +765,12 @@ extern "C" int divans_gpu_codec_set_encode_path(divans_gpu_codec* c, uint32_t pa
     return 0;
 }
 
+extern "C" int divans_gpu_codec_last_encode_path(divans_gpu_codec* c, uint32_t* path) {
+    if (!c || !path) return fail(DIVANS_GPU_EINVAL, "null argument");
+    *path = c->last_encode_path;
+    return 0;
+}
+
 extern "C" int divans_gpu_codec_set_bucket_batch(divans_gpu_codec* c, uint32_t streams) {
     if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
     if (streams == 0 || streams >= (1u << 24)) return fail(DIVANS_GPU_EINVAL, "bucket batch must be in [1, 2^24)");
@@ -1025,7 +1032,10 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
     int rc = maybe_learn_rank(c, d_in, d_in_offsets, d_in_sizes, n_streams, stream_len);     // byte order 0: the decoder's table order follows the data the codec sees
     if (rc) return rc;
     SfView view;
-    if (use_bucket(c) && n_streams < (1u << 24) && !d_segs) {   // segment lists (context reloads between Literal commands) go through the streaming kernels
+    // segment lists (context reloads between Literal commands) go through the streaming kernels unless the caller asked for the
+    // bucketed pass (divans_gpu_codec_set_encode_path(c, 2)): its sort kernels then take the keys of a segment's first bytes from last8
+    const bool segs_ok = !d_segs || c->encode_path == 2u;
+    if (use_bucket(c) && n_streams < (1u << 24) && segs_ok) {
         BucketBatch k;
         std::memset(&k, 0, sizeof(k));
         // launch sequences of at most bucket_mix_batch streams (work arrays are sized for one of them: 11.2 bytes per input byte of
@@ -1036,6 +1046,8 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
         k.pieces = bucket_pieces(c); k.slot = bucket_slot(c);
         k.sf = (uint32_t*)k.sfs; k.sf_stride = 2u * k.slot;     // bucket_unsort_kernel works in place
         k.inc = c->geom.inc0; k.lim = c->geom.lim0;
+        k.segs = (const LitSegment*)d_segs; k.bt_first = c->geom.bt_first; k.n_btypes = c->geom.n_btypes; k.status = c->d_status;
+        c->last_encode_path = 2u;
         view.sf = k.sf; view.stride = k.sf_stride;
         view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 3u;
         HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -1044,12 +1056,13 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
             k.in = d_in_offsets ? d_in : d_in + (size_t)s0 * stream_len;
             k.in_offsets = d_in_offsets ? d_in_offsets + s0 : nullptr;
             k.in_sizes = d_in_sizes ? d_in_sizes + s0 : nullptr;
+            k.seg_begin = d_seg_begin ? d_seg_begin + s0 : nullptr;
             HIP_TRY(launch_bucket_model(k, c->num_cus * 4u, c->stream));
             rc = after(s0, k.n_streams, view); if (rc) return rc;
         }
         return 0;
     }
-    if (use_bucket_mix(c) && !d_segs) {
+    if (use_bucket_mix(c) && segs_ok) {
         MixBucketBatch k;
         std::memset(&k, 0, sizeof(k));
         // as many streams per launch sequence as the device has room for: a bucket is a serial chain, and the longest
@@ -1061,6 +1074,8 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
         k.slot = bucket_slot(c); k.pos_stride = k.slot;
         k.sf = (uint32_t*)k.xs[0]; k.sf_stride = 2u * k.slot;  // mix_weights_kernel writes the pairs over the stride model's entries
         k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
+        k.segs = (const LitSegment*)d_segs; k.bt_first = c->geom.bt_first; k.n_btypes = c->geom.n_btypes; k.status = c->d_status;
+        c->last_encode_path = 3u;
         view.sf = k.sf; view.stride = k.sf_stride;
         view.spare = (uint8_t*)k.inv;
         HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -1069,6 +1084,7 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
             k.in = d_in_offsets ? d_in : d_in + (size_t)s0 * stream_len;
             k.in_offsets = d_in_offsets ? d_in_offsets + s0 : nullptr;
             k.in_sizes = d_in_sizes ? d_in_sizes + s0 : nullptr;
+            k.seg_begin = d_seg_begin ? d_seg_begin + s0 : nullptr;
             HIP_TRY(launch_bucket_mix_model(k, c->num_cus, c->stream));
             view.spare_bytes = (size_t)sub * k.slot * 4u;
             rc = after(s0, k.n_streams, view); if (rc) return rc;
@@ -1088,6 +1104,7 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
     if (d_segs && b.cache_mode != 2u && b.cache_mode != 0u) return fail(DIVANS_GPU_EINVAL, "segment lists need the default (high-nibble-row) cache or none");
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     ++c->table_launch_seq;
+    c->last_encode_path = 1u;
     HIP_TRY(launch_model_encode(b, c->mix, c->blocks, c->stream));
     view.sf = c->d_sf; view.stride = 2u * c->max_stream_len;
     return after(0u, n_streams, view);
@@ -1765,6 +1782,7 @@ extern "C" int divans_gpu_lit_stream_encode(divans_gpu_codec* c, const uint8_t* 
     b.resume = c->sp_started ? 1u : 0u; b.wstate = c->d_wstate;
     set_cache_fields(c, b);
     ++c->table_launch_seq;
+    c->last_encode_path = 1u;
     HIP_TRY(launch_model_encode(b, c->mix, 1u, c->stream));
     c->sp_started = true;
     c->sp_pending += 2u * len;

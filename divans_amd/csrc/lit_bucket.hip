@@ -22,20 +22,30 @@ namespace divans_hip {
 
 // ---------------------------------------------------------------------------------------------
 // 1. per (stream, piece): sorted[slot] = byte, inv[pos] = slot, desc[stream][prev][piece] = start | count << 16
+//    SEG: the stream has a segment list (b.seg_begin / b.segs): the first byte of every non-empty segment takes its key from the
+//    segment's last8 instead of the byte before it (SegCursor, lit_device.h), through an LDS copy of the keys that the workgroup
+//    patches while it walks the list (bk_seg_walk); the workgroup of piece 0 checks the list.  SEG = false is the code it was.
 // ---------------------------------------------------------------------------------------------
+template <bool SEG>
 __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const BucketBatch b) {
     __shared__ __attribute__((aligned(16))) unsigned long long staging64[BK_PIECE / 8u];   // lane masks while ranking, then the sorted bytes
     uint8_t* staging = (uint8_t*)staging64;
     __shared__ __attribute__((aligned(16))) uint8_t piece_in[16 + BK_PIECE];   // piece_in[15] = the byte before the piece
     __shared__ uint32_t hist[4][256];
     __shared__ uint32_t wsum[4];
+    __shared__ uint8_t prev_of[SEG ? BK_PIECE : 1u];     // SEG: the key of every position
     const uint32_t s = blockIdx.x / b.pieces, piece = blockIdx.x % b.pieces;
     const uint32_t tid = threadIdx.x, w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63;
     const uint32_t len = b.in_sizes ? b.in_sizes[s] : b.stream_len;
     const uint8_t* in = b.in + (b.in_offsets ? b.in_offsets[s] : (uint64_t)s * b.stream_len);
     uint32_t* desc = b.desc + ((size_t)s * 256u + tid) * 8u + piece;
     const uint32_t base = piece * BK_PIECE;
-    if (base >= len) { *desc = 0u; return; }
+    if (base >= len) {
+        *desc = 0u;
+        if (SEG && piece == 0u)     // an empty stream: its list still has to add up to it
+            bk_seg_walk(b.seg_begin, b.segs, s, 0u, ~0u, true, b.bt_first, b.n_btypes, b.status, wsum, [](uint32_t, uint32_t, uint64_t) {});
+        return;
+    }
     const uint32_t n = len - base < BK_PIECE ? len - base : BK_PIECE;
     const size_t pl = b.slot;
     for (uint32_t i = tid; i < 1024u; i += BK_SORT_THREADS) (&hist[0][0])[i] = 0u;
@@ -54,6 +64,13 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const Buck
     }
     __syncthreads();
     const uint8_t* key_of = piece_in + 15;      // key_of[p] = previous byte of position p, key_of[p + 1] = its own byte
+    if (SEG) {
+        for (uint32_t i = tid; i < n; i += BK_SORT_THREADS) prev_of[i] = key_of[i];
+        __syncthreads();
+        bk_seg_walk(b.seg_begin, b.segs, s, len, piece == 0u ? ~0u : base + n, piece == 0u, b.bt_first, b.n_btypes, b.status, wsum,
+                    [&](uint32_t q, uint32_t, uint64_t l8) { if (q - base < n) prev_of[q - base] = (uint8_t)(l8 >> 56); });
+        __syncthreads();
+    }
     // ONE ranking pass: wave w owns positions [2048 w, 2048 w + 2048) of the piece and visits them in order, 64 at a time.  The lanes
     // that hold the same key find each other through the wave's 256 lane masks in LDS (in `staging`, which is free until placement):
     // every lane clears its key's mask, ORs its own bit in and reads the mask back -- three LDS operations in program order, against the
@@ -70,7 +87,7 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const Buck
         uint32_t r = 0;
         const uint32_t p = w * 2048u + bt * 64u + lane;
         if (p < n) {
-            const uint32_t key = key_of[p];
+            const uint32_t key = SEG ? prev_of[p] : key_of[p];
             __hip_atomic_store(mask_of + key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_or(mask_of + key, my_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const unsigned long long same = __hip_atomic_load(mask_of + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -103,7 +120,7 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const Buck
     for (uint32_t bt = 0; bt < 32u; ++bt) {
         const uint32_t p = w * 2048u + bt * 64u + lane;
         if (p < n) {
-            const uint32_t key = key_of[p], byte = key_of[p + 1u];
+            const uint32_t key = SEG ? prev_of[p] : key_of[p], byte = key_of[p + 1u];
             const uint32_t slot = hist[w][key] + ((kept[bt >> 1] >> (16u * (bt & 1u))) & 0xffffu);
             staging[slot] = (uint8_t)byte;
             inv[p] = (uint16_t)slot;
@@ -116,6 +133,10 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const Buck
         else for (uint32_t k = i; k < n; ++k) sorted[k] = staging[k];
     }
 }
+
+// (instantiated here, the SEG instance where launch_bucket_model names it -- behind every other kernel of the file: the kernels of
+// the default path keep their places in the code object)
+template __global__ void bucket_sort_kernel<false>(const BucketBatch b);
 
 // ---------------------------------------------------------------------------------------------
 // 2. task lists by bucket size class, so that the long chains start first
@@ -376,7 +397,8 @@ hipError_t launch_bucket_model(const BucketBatch& b, uint32_t chain_blocks, hipS
         e = hipMemsetAsync(b.desc, 0, (size_t)b.n_streams * 256u * 8u * sizeof(uint32_t), st);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(bucket_sort_kernel, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
+    if (b.segs) hipLaunchKernelGGL(bucket_sort_kernel<true>, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
+    else hipLaunchKernelGGL(bucket_sort_kernel<false>, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
     hipLaunchKernelGGL(bucket_tasks_kernel, dim3((b.n_streams + 3u) / 4u), dim3(1024), 0, st, b);
 #if DIVANS_BK_CHAIN_NO_STORES   // every pair reads (start 1, freq 2048): the rANS pass stays inside its slots on the pairs nobody wrote
     e = hipMemsetD32Async((hipDeviceptr_t)b.sfs, (int)(1u | (2048u << 16)), (size_t)b.n_streams * b.slot * 2u, st);

@@ -40,6 +40,49 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// The SEG = true sort kernels: the whole workgroup (BK_SORT_THREADS lanes) walks the segment list of ITS stream, 256 segments per
+// step with a block-wide running sum of `len`, and calls patch(q, len, last8) -- by the lane that holds the segment -- for every
+// NON-EMPTY segment that starts at an offset q below the stream's length: such a segment installs its last8 as the history of
+// position q (SegCursor::advance, lit_device.h; empty segments install nothing that lasts).  The walk ends after the step in which
+// the running sum passes `until` (no later segment starts below it).  With `check` (one workgroup per stream: until = ~0u) it walks
+// the whole list and raises LIT_STATUS_BAD_SEGMENT where the lengths do not add up to `len` or a segment names a block type outside
+// [bt_first, bt_first + n_btypes).  A length is clamped to 65 537 (> any stream of the bucketed passes: the verdict is the same) and
+// the walk stops once the sum has passed the stream's length, so the sum stays far inside 32 bits however long the list is.
+// `wsum` = four words of LDS; every lane of the workgroup must call this (it synchronises).
+template <class Patch>
+__device__ __forceinline__ void bk_seg_walk(const uint32_t* seg_begin, const LitSegment* segs, uint32_t s, uint32_t len, uint32_t until, bool check,
+                                            uint32_t bt_first, uint32_t n_btypes, uint32_t* status, uint32_t* wsum, Patch&& patch) {
+    const uint32_t tid = threadIdx.x, w = tid >> 6, lane = tid & 63u;
+    const uint32_t first = seg_begin[s], end = seg_begin[s + 1u];
+    uint32_t run = 0u;
+    bool bad = false;
+    for (uint32_t i0 = first; i0 < end; i0 += BK_SORT_THREADS) {       // workgroup-uniform
+        const uint32_t i = i0 + tid;
+        u32x4 sg = {0u, 0u, 0u, 0u};
+        if (i < end) {
+            sg = *(const u32x4*)(segs + i);
+            if (sg.y - bt_first >= n_btypes) bad = true;
+        }
+        const uint32_t l = sg.x < 65537u ? sg.x : 65537u;
+        uint32_t incl = l;
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= d) incl += v;
+        }
+        if (lane == 63u) wsum[w] = incl;
+        __syncthreads();
+        const uint32_t s0 = wsum[0], s1 = wsum[1], s2 = wsum[2], s3 = wsum[3];
+        const uint32_t q = run + (w > 0u ? s0 : 0u) + (w > 1u ? s1 : 0u) + (w > 2u ? s2 : 0u) + incl - l;
+        if (l != 0u && q < len) patch(q, l, ((uint64_t)sg.w << 32) | sg.z);
+        run += s0 + s1 + s2 + s3;
+        __syncthreads();
+        if (run > len || run >= until) break;
+    }
+    if (check) {
+        if (bad || (run != len && tid == 0u)) atomicOr(status, LIT_STATUS_BAD_SEGMENT);
+    }
+}
+
 // One nibble against a row of 8 dwords (16 x u16) in LDS, split into phases so that the two nibbles of a byte
 // (different rows) can be in flight together: read, pack (start | freq << 16), blend, write.
 struct BkRow { u32x4 w0, w1, a0, a1; int chi, cprev; };

@@ -36,8 +36,12 @@ template <int MODEL> struct MxGeom {
 // ---------------------------------------------------------------------------------------------
 // 1. per (stream, piece): sorted[slot] = byte | high-row slot << 8, inv[pos] = slot, desc[stream][key][piece]
 //    MODEL 0 (stride): key = prev.  MODEL 1 (context map): key = ctx (literal.rs:87-117 through the fused table).
+//    SEG: the stream has a segment list: the first byte of every non-empty segment takes prev and prev_prev from the segment's last8,
+//    its second byte prev_prev (SegCursor, lit_device.h).  The keys are first formed from the bytes themselves, then the workgroup
+//    walks the list (bk_seg_walk) and forms those two positions' keys again, and only then counts them; the workgroup of piece 0
+//    checks the list.  SEG = false is the code it was.
 // ---------------------------------------------------------------------------------------------
-template <int MODEL>
+template <int MODEL, bool SEG>
 __global__ __launch_bounds__(BK_SORT_THREADS) void mix_sort_kernel(const MixBucketBatch b) {
     __shared__ __attribute__((aligned(16))) uint16_t staging[BK_PIECE];
     __shared__ __attribute__((aligned(16))) uint8_t piece_in[16 + BK_PIECE];   // piece_in[14], [15] = the two bytes before the piece
@@ -51,7 +55,12 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void mix_sort_kernel(const MixBuck
     const uint8_t* in = b.in + (b.in_offsets ? b.in_offsets[s] : (uint64_t)s * b.stream_len);
     uint32_t* desc = b.desc + ((size_t)s * 256u + tid) * 8u + piece;
     const uint32_t base = piece * BK_PIECE;
-    if (base >= len) { *desc = 0u; return; }
+    if (base >= len) {
+        *desc = 0u;
+        if (SEG && piece == 0u)     // an empty stream: its list still has to add up to it
+            bk_seg_walk(b.seg_begin, b.segs, s, 0u, ~0u, true, b.bt_first, b.n_btypes, b.status, scan, [](uint32_t, uint32_t, uint64_t) {});
+        return;
+    }
     const uint32_t n = len - base < BK_PIECE ? len - base : BK_PIECE;
     const size_t pl = b.slot;
     for (uint32_t i = tid; i < 1024u; i += BK_SORT_THREADS) (&hist[0][0])[i] = 0u;
@@ -86,10 +95,30 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void mix_sort_kernel(const MixBuck
             const uint32_t prev = piece_in[15u + p], e = (prev << 3) + lut1c[piece_in[14u + p]];
             const uint32_t key = MODEL == 0 ? prev : ctxf[e];
             kp[p] = (uint16_t)(key | (MODEL == 0 ? (uint32_t)slot_of[e] << 8 : 0u));
-            atomicAdd(&hist[w][key], 1u);
+            if (!SEG) atomicAdd(&hist[w][key], 1u);
         }
     }
     __syncthreads();
+    if (SEG) {
+        const auto kp_of = [&](uint32_t prev, uint32_t prev_prev) -> uint16_t {
+            const uint32_t e = (prev << 3) + lut1c[prev_prev];
+            return (uint16_t)((MODEL == 0 ? prev : (uint32_t)ctxf[e]) | (MODEL == 0 ? (uint32_t)slot_of[e] << 8 : 0u));
+        };
+        // a segment of one byte leaves its second position to the segment that follows: every position is written by one lane at most
+        bk_seg_walk(b.seg_begin, b.segs, s, len, piece == 0u ? ~0u : base + n, piece == 0u, b.bt_first, b.n_btypes, b.status, scan,
+                    [&](uint32_t q, uint32_t l, uint64_t l8) {
+                        const uint32_t newest = (uint32_t)(l8 >> 56), before = (uint32_t)(l8 >> 48) & 0xffu;
+                        const uint32_t p = q - base, p1 = q + 1u - base;
+                        if (p < n) kp[p] = kp_of(newest, before);
+                        if (l >= 2u && p1 < n) kp[p1] = kp_of(piece_in[15u + p1], newest);
+                    });
+        __syncthreads();
+        for (uint32_t bt = 0; bt < 32u; ++bt) {
+            const uint32_t p = w * 2048u + bt * 64u + lane;
+            if (p < n) atomicAdd(&hist[w][kp[p] & 0xffu], 1u);
+        }
+        __syncthreads();
+    }
     const uint32_t c0 = hist[0][tid], c1 = hist[1][tid], c2 = hist[2][tid], c3 = hist[3][tid];
     const uint32_t tot = c0 + c1 + c2 + c3;
     scan[tid] = tot;
@@ -527,6 +556,10 @@ hipError_t launch_selftest_cdf_ops_bucket(const uint32_t* d_ops, uint32_t n, int
     return hipGetLastError();
 }
 
+// defined behind launch_bucket_mix_model: the SEG instances are then instantiated behind every other kernel of the file, and the
+// kernels of the default path keep their places in the code object
+static void launch_mix_sort_seg(int model, const MixBucketBatch& b, hipStream_t st);
+
 hipError_t launch_bucket_mix_model(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st) {
     BucketBatch v;                       // the view the shared task-list and unsort kernels take
     v.in = b.in; v.in_offsets = b.in_offsets; v.in_sizes = b.in_sizes;
@@ -534,6 +567,7 @@ hipError_t launch_bucket_mix_model(const MixBucketBatch& b, uint32_t num_cus, hi
     v.slot = b.slot; v.sf_stride = 2u * b.pos_stride;   // pos_stride == slot: the unsort below is in place
     v.sorted = nullptr; v.inv = b.inv; v.desc = b.desc; v.sfs = nullptr; v.sf = nullptr; v.tasks = b.tasks; v.counters = b.counters;
     v.inc = 0; v.lim = 0;
+    v.seg_begin = nullptr; v.segs = nullptr; v.bt_first = 0; v.n_btypes = 0; v.status = nullptr;   // (the sort kernels here take `b`)
     for (int model = 0; model < 2; ++model) {
         hipError_t e = hipMemsetAsync(b.counters, 0, 64, st);
         if (e != hipSuccess) return e;
@@ -542,11 +576,13 @@ hipError_t launch_bucket_mix_model(const MixBucketBatch& b, uint32_t num_cus, hi
             if (e != hipSuccess) return e;
         }
         if (model == 0) {
-            hipLaunchKernelGGL(mix_sort_kernel<0>, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
+            if (b.segs) launch_mix_sort_seg(0, b, st);
+            else hipLaunchKernelGGL((mix_sort_kernel<0, false>), dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
             launch_bucket_tasks(v, st);
             hipLaunchKernelGGL(mix_chain_kernel<0>, dim3(num_cus * MX_CHAIN_WAVES), dim3(64), MxGeom<0>::LDS_BYTES, st, b);
         } else {
-            hipLaunchKernelGGL(mix_sort_kernel<1>, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
+            if (b.segs) launch_mix_sort_seg(1, b, st);
+            else hipLaunchKernelGGL((mix_sort_kernel<1, false>), dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
             launch_bucket_tasks(v, st);
             hipLaunchKernelGGL(mix_chain_kernel<1>, dim3(num_cus * MX_CHAIN_WAVES), dim3(64), MxGeom<1>::LDS_BYTES, st, b);
         }
@@ -558,6 +594,11 @@ hipError_t launch_bucket_mix_model(const MixBucketBatch& b, uint32_t num_cus, hi
     if ((b.n_streams + 31u) / 32u > num_cus * 4u) hipLaunchKernelGGL(mix_weights_kernel<2>, dim3((b.n_streams + 31u) / 32u), dim3(64), 0, st, b);
     else hipLaunchKernelGGL(mix_weights_kernel<1>, dim3((b.n_streams + 31u) / 32u), dim3(64), 0, st, b);
     return hipGetLastError();
+}
+
+static void launch_mix_sort_seg(int model, const MixBucketBatch& b, hipStream_t st) {
+    if (model == 0) hipLaunchKernelGGL((mix_sort_kernel<0, true>), dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
+    else hipLaunchKernelGGL((mix_sort_kernel<1, true>), dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
 }
 
 }  // namespace divans_hip

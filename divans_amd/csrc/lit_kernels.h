@@ -98,6 +98,7 @@ struct RansBatch {
 
 typedef unsigned int bk_u32x2 __attribute__((ext_vector_type(2)));
 // Bucketed encoder model pass (lit_bucket.hip): mixing value 4, no mixing, context constant or a function of the previous byte.
+// With a segment list only the sort kernel changes: a segment's last8 replaces the bytes before its first position in the bucket keys.
 struct BucketBatch {
     const uint8_t* in; const uint64_t* in_offsets; const uint32_t* in_sizes;
     uint32_t n_streams, stream_len, max_stream_len;
@@ -112,6 +113,11 @@ struct BucketBatch {
     uint32_t* tasks;            // [6 size classes][n_streams * 256] stream * 256 + previous byte
     uint32_t* counters;         // [0..5] tasks per class, [8] next unclaimed task
     int32_t inc, lim;           // literal_adaptation[0]
+    // general streams (bucket_sort_kernel<true>), or null: every stream is one segment with zero history
+    const uint32_t* seg_begin;  // [n_streams + 1] first segment of every stream in `segs` (the caller's array, offset like in_offsets)
+    const LitSegment* segs;
+    uint32_t bt_first, n_btypes;   // the block types a segment may name (LitGeometry); they do not enter the keys
+    uint32_t* status;           // device word: LIT_STATUS_BAD_SEGMENT
 };
 hipError_t launch_bucket_model(const BucketBatch& b, uint32_t chain_blocks, hipStream_t st);
 void launch_bucket_tasks(const BucketBatch& b, hipStream_t st);
@@ -119,7 +125,8 @@ void launch_bucket_unsort(const BucketBatch& b, hipStream_t st);
 void launch_bucket_unsort32(const BucketBatch& b, hipStream_t st);   // the same for a plane of 4-byte elements
 
 // Bucketed encoder model pass for the two-model configuration (lit_bucket_mix.hip): context map on, every mixing value 4
-// (stride 1), dynamic mixing (context_mixing >= 2), one literal block type, no segment lists, streams <= 64 KiB.
+// (stride 1), dynamic mixing (context_mixing >= 2), one literal block type, streams <= 64 KiB.  With a segment list only the sort
+// kernels change: a segment's last8 replaces the two bytes before its first position in the keys and high-row slots.
 struct MixBucketBatch {
     const uint8_t* in; const uint64_t* in_offsets; const uint32_t* in_sizes;
     uint32_t n_streams, stream_len, max_stream_len;
@@ -143,6 +150,11 @@ struct MixBucketBatch {
     uint32_t* sf;               // [n_streams][sf_stride] what rans_encode_kernel reads; may be xs[0] (mix_weights_kernel reads a
                                 // chunk of all four planes before it writes that chunk's pairs)
     int32_t inc0, lim0, inc2, lim2, inc3, lim3;   // literal_adaptation[0] (stride rows), [2] (cm low), [3] (cm high)
+    // general streams (mix_sort_kernel<MODEL, true>), or null; as in BucketBatch
+    const uint32_t* seg_begin;
+    const LitSegment* segs;
+    uint32_t bt_first, n_btypes;
+    uint32_t* status;
 };
 hipError_t launch_bucket_mix_model(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st);
 

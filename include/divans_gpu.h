@@ -114,7 +114,9 @@ int divans_gpu_codec_set_block_types(divans_gpu_codec *c, uint32_t n_btypes);
  * by the segments d_segs[d_seg_begin[i] .. d_seg_begin[i+1]) (device arrays; d_seg_begin has n_streams + 1 entries).
  * The lengths of a stream's segments add up to its size (an empty stream has no segments or empty ones only): a list that
  * covers fewer or more bytes raises DIVANS_GPU_STATUS_BAD_SEGMENT in the status word, in both directions -- the stream was
- * coded under a context the list did not say; the other streams of the batch are not affected. */
+ * coded under a context the list did not say; the other streams of the batch are not affected.
+ * The encoder codes a list with its streaming kernels unless divans_gpu_codec_set_encode_path(c, 2) asked for the bucketed model
+ * pass (same bytes, same status contract; the row-cache organisation then plays no part). */
 int divans_gpu_lit_encode_segments_batch(divans_gpu_codec *c, const uint8_t *d_in, const uint64_t *d_in_offsets,
                                          const uint32_t *d_in_sizes, uint32_t stream_len, uint32_t n_streams,
                                          const uint32_t *d_seg_begin, const divans_lit_segment *d_segs,
@@ -238,8 +240,13 @@ int divans_gpu_codec_set_geometry(divans_gpu_codec *c, uint32_t blocks, uint32_t
  * (stride 1) and streams of at most 65536 bytes: without mixing when the context is constant or follows from the previous
  * byte alone (divans_lit_config_simple; LSB6 / MSB6 prediction modes with any context map, i.e. what the literal-only
  * compressor emits), or with a context map and dynamic mixing for one literal block type (divans_lit_config_context_mixing).  There it is what
- * "automatic" picks; asking for it elsewhere is DIVANS_GPU_EINVAL.  Both produce the same bytes. */
+ * "automatic" picks for calls without a segment list; asking for it elsewhere is DIVANS_GPU_EINVAL.  Both produce the same bytes.
+ * A call WITH a segment list (divans_gpu_lit_encode_segments_batch) takes the bucketed pass only under path 2 -- a segment's last8
+ * then replaces the bytes before its first position in the bucket keys -- and the streaming kernels under "automatic". */
 int divans_gpu_codec_set_encode_path(divans_gpu_codec *c, uint32_t path);
+/* The model pass the last encode / model call of this codec ran: 0 = none yet, 1 = streaming kernels, 2 = bucketed one-model
+ * pass (lit_bucket.hip), 3 = bucketed two-model pass (lit_bucket_mix.hip). */
+int divans_gpu_codec_last_encode_path(divans_gpu_codec *c, uint32_t *path);
 /* Streams the bucketed two-model pass takes per launch sequence (default 32768, halved until its work arrays -- 1.9 MB
  * per 64 KiB stream -- fit the device).  A tuning / test knob: the coded bytes do not depend on it. */
 int divans_gpu_codec_set_bucket_batch(divans_gpu_codec *c, uint32_t streams);
