@@ -658,23 +658,27 @@ static uint32_t bucket_slot(const divans_gpu_codec* c) { return bucket_pieces(c)
 static bool use_bucket_mix(const divans_gpu_codec* c) { return c->bucket_mix_ok && c->encode_path != 1u && !c->geom.wrap_check; }
 static bool use_bucket(const divans_gpu_codec* c) { return c->bucket_ok && c->encode_path != 1u && !c->geom.wrap_check; }   // task ids are stream * 256 + byte in 32 bits: callers keep n_streams < 2^24
 
-// one allocation carved into the five work arrays of BucketBatch
+// The bucketed passes' work arrays are one allocation (c->d_bk) that only grows; each pass carves it in its own order.
+static int ensure_bucket_bytes(divans_gpu_codec* c, size_t need, const char* oom) {
+    if (need > c->bk_bytes) {
+        if (c->d_bk) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_bk)); c->d_bk = nullptr; c->bk_bytes = 0; }
+        if (device_alloc((void**)&c->d_bk, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, oom);
+        c->bk_bytes = need;
+    }
+    return 0;
+}
+
 static int ensure_bucket(divans_gpu_codec* c, uint32_t n_streams, BucketBatch& b) {
     const size_t pl = bucket_slot(c);
     const size_t n = n_streams;
     const size_t sz_sfs = n * pl * 8u, sz_desc = n * 256u * 8u * 4u, sz_tasks = n * 256u * 6u * 4u, sz_inv = n * pl * 2u, sz_sorted = n * pl;
-    const size_t need = sz_sfs + sz_desc + sz_tasks + sz_inv + sz_sorted + 256u;
-    if (need > c->bk_bytes) {
-        if (c->d_bk) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_bk)); c->d_bk = nullptr; c->bk_bytes = 0; }
-        if (device_alloc((void**)&c->d_bk, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(bucketed encoder work arrays) failed");
-        c->bk_bytes = need;
-    }
+    if (int rc = ensure_bucket_bytes(c, sz_sfs + sz_desc + sz_tasks + sz_inv + sz_sorted + 256u, "hipMalloc(bucketed encoder work arrays) failed")) return rc;
     uint8_t* p = c->d_bk;
     b.counters = (uint32_t*)p; p += 256;
     b.sfs = (bk_u32x2*)p; p += sz_sfs;
     b.desc = (uint32_t*)p; p += sz_desc;
     b.tasks = (uint32_t*)p; p += sz_tasks;
-    b.inv = (uint16_t*)p; p += sz_inv;
+    b.inv = (uint16_t*)p; p += sz_inv;       // inv and sorted stay adjacent: together they are the rANS pass's scratch (SfView::spare)
     b.sorted = p;
     return 0;
 }
@@ -683,19 +687,14 @@ static int ensure_bucket_mix(divans_gpu_codec* c, uint32_t n_streams, MixBucketB
     const size_t pl = bucket_slot(c);
     const size_t n = n_streams;
     const size_t sz_xs = n * pl * 8u, sz_max = n * pl * 4u, sz_desc = n * 256u * 8u * 4u, sz_tasks = n * 256u * 6u * 4u, sz_inv = n * pl * 2u, sz_sorted = n * pl * 2u;
-    const size_t need = 256u + 2u * (sz_xs + sz_max) + sz_desc + sz_tasks + sz_inv + sz_sorted;
-    if (need > c->bk_bytes) {
-        if (c->d_bk) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_bk)); c->d_bk = nullptr; c->bk_bytes = 0; }
-        if (device_alloc((void**)&c->d_bk, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(bucketed two-model encoder work arrays) failed");
-        c->bk_bytes = need;
-    }
+    if (int rc = ensure_bucket_bytes(c, 256u + 2u * (sz_xs + sz_max) + sz_desc + sz_tasks + sz_inv + sz_sorted, "hipMalloc(bucketed two-model encoder work arrays) failed")) return rc;
     uint8_t* p = c->d_bk;
     b.counters = (uint32_t*)p; p += 256;
     for (int i = 0; i < 2; ++i) { b.xs[i] = (bk_u32x2*)p; p += sz_xs; }      // 12 bytes per position and model: the entries, then the row totals
     for (int i = 0; i < 2; ++i) { b.maxes[i] = (uint32_t*)p; p += sz_max; }
     b.desc = (uint32_t*)p; p += sz_desc;
     b.tasks = (uint32_t*)p; p += sz_tasks;
-    b.inv = (uint16_t*)p; p += sz_inv;       // inv and sorted stay adjacent: together they are the rANS pass's scratch (SfView::spare)
+    b.inv = (uint16_t*)p; p += sz_inv;       // as in ensure_bucket
     b.sorted = (uint16_t*)p;
     return 0;
 }
@@ -1022,10 +1021,35 @@ extern "C" size_t divans_gpu_lit_encode_bound(size_t n) {
     return (bytes + 15) & ~(size_t)15;
 }
 
+// the fields BucketBatch and MixBucketBatch have in common (the per-sub-batch ones are set by bucket_sub_batches)
+template <class Batch>
+static void fill_bucket_batch(const divans_gpu_codec* c, uint32_t stream_len, const divans_lit_segment* d_segs, Batch& k) {
+    k.stream_len = stream_len; k.max_stream_len = c->max_stream_len;
+    k.pieces = bucket_pieces(c); k.slot = bucket_slot(c);
+    k.segs = (const LitSegment*)d_segs; k.bt_first = c->geom.bt_first; k.n_btypes = c->geom.n_btypes; k.status = c->d_status;
+}
+
+// A bucketed pass works through the batch in launch sequences of at most `sub` streams, whose work arrays it reuses: whatever consumes
+// a sequence's pairs (`after`) is enqueued before the next one's kernels (`launch`).  Records ev[0] before the first kernel.
+template <class Batch, class Launch, class After>
+static int bucket_sub_batches(divans_gpu_codec* c, Batch& k, uint32_t sub, const SfView& view, const uint8_t* d_in, const uint64_t* d_in_offsets,
+                              const uint32_t* d_in_sizes, const uint32_t* d_seg_begin, uint32_t n_streams, Launch&& launch, After&& after) {
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    for (uint32_t s0 = 0; s0 < n_streams; s0 += sub) {
+        k.n_streams = std::min(sub, n_streams - s0);
+        k.in = d_in_offsets ? d_in : d_in + (size_t)s0 * k.stream_len;
+        k.in_offsets = d_in_offsets ? d_in_offsets + s0 : nullptr;
+        k.in_sizes = d_in_sizes ? d_in_sizes + s0 : nullptr;
+        k.seg_begin = d_seg_begin ? d_seg_begin + s0 : nullptr;
+        if (int rc = launch(k)) return rc;
+        if (int rc = after(s0, k.n_streams, view)) return rc;
+    }
+    return 0;
+}
+
 // Encoder pass 1: (start | freq << 16) per nibble, position order.  `after(first, count, view)` is called once the model kernels
-// of streams [first, first + count) are enqueued (the two-model bucketed pass works through the batch in sub-batches whose
-// work arrays it reuses, so whatever consumes the pairs has to be enqueued in between); the bucketed passes leave the pairs in
-// their own work arrays (the unsort is in place), the streaming kernels in c->d_sf.  Records ev[0] before the first kernel.
+// of streams [first, first + count) are enqueued (the bucketed passes work through the batch in sub-batches, bucket_sub_batches);
+// they leave the pairs in their own work arrays (the unsort is in place), the streaming kernels in c->d_sf.  Records ev[0] first.
 template <class After>
 static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets, const uint32_t* d_in_sizes,
                       uint32_t stream_len, uint32_t n_streams, const uint32_t* d_seg_begin, const divans_lit_segment* d_segs, After&& after) {
@@ -1038,29 +1062,17 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
     if (use_bucket(c) && n_streams < (1u << 24) && segs_ok) {
         BucketBatch k;
         std::memset(&k, 0, sizeof(k));
-        // launch sequences of at most bucket_mix_batch streams (work arrays are sized for one of them: 11.2 bytes per input byte of
-        // 32 768 streams instead of the whole batch's; whatever consumes the pairs is enqueued in between, as in the two-model pass)
+        // launch sequences of at most bucket_mix_batch streams: work arrays of 11.2 bytes per input byte of 32 768 streams, not of the batch
         const uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
         rc = ensure_bucket(c, sub, k); if (rc) return rc;
-        k.stream_len = stream_len; k.max_stream_len = c->max_stream_len;
-        k.pieces = bucket_pieces(c); k.slot = bucket_slot(c);
+        fill_bucket_batch(c, stream_len, d_segs, k);
         k.sf = (uint32_t*)k.sfs; k.sf_stride = 2u * k.slot;     // bucket_unsort_kernel works in place
         k.inc = c->geom.inc0; k.lim = c->geom.lim0;
-        k.segs = (const LitSegment*)d_segs; k.bt_first = c->geom.bt_first; k.n_btypes = c->geom.n_btypes; k.status = c->d_status;
         c->last_encode_path = 2u;
         view.sf = k.sf; view.stride = k.sf_stride;
         view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 3u;
-        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-        for (uint32_t s0 = 0; s0 < n_streams; s0 += sub) {
-            k.n_streams = std::min(sub, n_streams - s0);
-            k.in = d_in_offsets ? d_in : d_in + (size_t)s0 * stream_len;
-            k.in_offsets = d_in_offsets ? d_in_offsets + s0 : nullptr;
-            k.in_sizes = d_in_sizes ? d_in_sizes + s0 : nullptr;
-            k.seg_begin = d_seg_begin ? d_seg_begin + s0 : nullptr;
-            HIP_TRY(launch_bucket_model(k, c->num_cus * 4u, c->stream));
-            rc = after(s0, k.n_streams, view); if (rc) return rc;
-        }
-        return 0;
+        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
+                                  [&](const BucketBatch& kk) -> int { HIP_TRY(launch_bucket_model(kk, c->num_cus * 4u, c->stream)); return 0; }, after);
     }
     if (use_bucket_mix(c) && segs_ok) {
         MixBucketBatch k;
@@ -1070,26 +1082,15 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
         uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
         while ((rc = ensure_bucket_mix(c, sub, k)) == DIVANS_GPU_ENOMEM && sub > 1024u) { (void)hipGetLastError(); sub = (sub + 1u) / 2u; }
         if (rc) return rc;
-        k.blob = c->d_blob; k.stream_len = stream_len; k.max_stream_len = c->max_stream_len; k.pieces = bucket_pieces(c);
-        k.slot = bucket_slot(c); k.pos_stride = k.slot;
+        fill_bucket_batch(c, stream_len, d_segs, k);
+        k.blob = c->d_blob; k.pos_stride = k.slot;
         k.sf = (uint32_t*)k.xs[0]; k.sf_stride = 2u * k.slot;  // mix_weights_kernel writes the pairs over the stride model's entries
         k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
-        k.segs = (const LitSegment*)d_segs; k.bt_first = c->geom.bt_first; k.n_btypes = c->geom.n_btypes; k.status = c->d_status;
         c->last_encode_path = 3u;
         view.sf = k.sf; view.stride = k.sf_stride;
-        view.spare = (uint8_t*)k.inv;
-        HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-        for (uint32_t s0 = 0; s0 < n_streams; s0 += sub) {
-            k.n_streams = std::min(sub, n_streams - s0);
-            k.in = d_in_offsets ? d_in : d_in + (size_t)s0 * stream_len;
-            k.in_offsets = d_in_offsets ? d_in_offsets + s0 : nullptr;
-            k.in_sizes = d_in_sizes ? d_in_sizes + s0 : nullptr;
-            k.seg_begin = d_seg_begin ? d_seg_begin + s0 : nullptr;
-            HIP_TRY(launch_bucket_mix_model(k, c->num_cus, c->stream));
-            view.spare_bytes = (size_t)sub * k.slot * 4u;
-            rc = after(s0, k.n_streams, view); if (rc) return rc;
-        }
-        return 0;
+        view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 4u;
+        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
+                                  [&](const MixBucketBatch& kk) -> int { HIP_TRY(launch_bucket_mix_model(kk, c->num_cus, c->stream)); return 0; }, after);
     }
     rc = ensure_sf(c, n_streams); if (rc) return rc;
     rc = ensure_tables(c); if (rc) return rc;

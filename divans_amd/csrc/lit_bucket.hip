@@ -8,7 +8,8 @@
 //   1. bucket_sort_kernel    stable counting sort of every 8 KiB piece of a stream by prev byte (LDS),
 //   2. bucket_tasks_kernel   turns the non-empty (stream, prev) buckets into a task list, longest first,
 //   3. bucket_chain_kernel   ONE LANE per bucket walks its positions in order with the bucket's 17 rows
-//                            (1 high + 16 low) in LDS -- no table in HBM, no row cache, no cross-lane traffic,
+//                            (1 high + 16 low) in LDS -- no table in HBM, no row cache, no cross-lane traffic (the loop
+//                            is explained at bk_chain_loop, lit_bucket_dev.h, which the two-model pass runs),
 //   4. bucket_unsort_kernel  puts the (start,freq) pairs back into position order for the rANS pass.
 // The arithmetic per nibble is the same as everywhere else (probability/interface.rs:97-108, frequentist_cdf.rs:74-85).
 // The decoder cannot do this (it learns the bytes one at a time) and keeps the streaming kernels.
@@ -49,19 +50,9 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_kernel(const Buck
     const uint32_t n = len - base < BK_PIECE ? len - base : BK_PIECE;
     const size_t pl = b.slot;
     for (uint32_t i = tid; i < 1024u; i += BK_SORT_THREADS) (&hist[0][0])[i] = 0u;
-    // the piece (and the byte before it: the first key) once into LDS, 16 bytes per lane where alignment allows
-    {
-        const uint8_t* src = in + base;
-        if ((((uintptr_t)src) & 15u) == 0u) {
-            for (uint32_t i = tid * 16u; i < n; i += BK_SORT_THREADS * 16u) {
-                if (i + 16u <= n) *(u32x4*)(piece_in + 16u + i) = *(const u32x4*)(src + i);
-                else for (uint32_t k = i; k < n; ++k) piece_in[16u + k] = src[k];
-            }
-        } else {
-            for (uint32_t i = tid; i < n; i += BK_SORT_THREADS) piece_in[16u + i] = src[i];
-        }
-        if (tid == 0u) piece_in[15] = base ? in[base - 1u] : 0u;
-    }
+    // the piece (and the byte before it: the first key) once into LDS
+    bk_load_piece(piece_in, in + base, n);
+    if (tid == 0u) piece_in[15] = base ? in[base - 1u] : 0u;
     __syncthreads();
     const uint8_t* key_of = piece_in + 15;      // key_of[p] = previous byte of position p, key_of[p + 1] = its own byte
     if (SEG) {
@@ -172,8 +163,15 @@ __global__ __launch_bounds__(1024) void bucket_tasks_kernel(const BucketBatch b)
 }
 
 // ---------------------------------------------------------------------------------------------
-// 3. chains
+// 3. chains.  This kernel holds the chain loop as its OWN text: the same loop, statement for statement, as bk_chain_loop
+//    (lit_bucket_dev.h), which both two-model chain kernels run and where the reasons for its shape are written down; change the
+//    two together.  On bk_chain_loop this kernel compiles to other instructions and its pass measured 0.35-0.75 ms slower per
+//    65 536 streams (profiles/r09_bench_ab.txt).  The group store and the row reset are shared: they leave its instructions as they were.
 // ---------------------------------------------------------------------------------------------
+constexpr uint32_t BK_LANE_DWORDS = 148;     // 17 rows x 8 dwords + 8 descriptors, padded: 16-byte aligned and the
+                                             // 64 lanes' b128 accesses at equal offsets cover all 32 banks
+constexpr uint32_t BK_DESC_DW = 136;
+constexpr uint32_t BK_TAB_DW = 64 * BK_LANE_DWORDS;
 __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds32[];
     const uint32_t lane = threadIdx.x;
@@ -189,11 +187,8 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
     const uint32_t cap = b.n_streams * 256u;
     BkTaskLists lists; lists.load(b.counters);
     const uint32_t total = lists.total();
-    const u32x4 def0 = {4u | (8u << 16), 12u | (16u << 16), 20u | (24u << 16), 28u | (32u << 16)};
-    const u32x4 def1 = {36u | (40u << 16), 44u | (48u << 16), 52u | (56u << 16), 60u | (64u << 16)};
 
-    // per-lane chain state.  A bucket is up to eight runs of consecutive sorted slots, one per 8 KiB piece that holds some of its
-    // positions; the task's descriptors are compacted to the non-empty ones when the lane takes it (mydesc[0 .. nruns)).
+    // per-lane chain state
     bool has_task = false, exhausted = false;
     uint32_t run_i = 0, nruns = 0, left = 0, idx = 0;
     u32x2* cur_sfs = b.sfs; const uint8_t* cur_sorted = b.sorted;   // the current bucket's stream slot
@@ -203,12 +198,6 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
     uint32_t win_cur = 0, win_end = 0, nxt_val = 0, nxt_w = 0;
     const uint32_t long_end = lists.ends[3];     // tasks of at least 2048 positions come first
     bool nxt_pending = false, drained = false;
-    // The chain is bound by the vector-memory path, not by its arithmetic (profiles/r03c_chain_role_experiment.txt), so a lane
-    // moves its bytes eight at a time: ONE aligned 8-byte load per iteration covers the sorted slots [base, base + 8), of which
-    // the run owns [first, first + cnt); it is requested one iteration before it is coded.  The (start, freq) pairs of a group
-    // leave at the top of the NEXT iteration -- four 16-byte stores for a full group -- through inline asm: the compiler then sees
-    // one load per iteration and waits for it with vmcnt(0) at a point where the only other operations in flight are stores a whole
-    // iteration old (a store is acknowledged out of order with loads, so no smaller count would prove the load complete).
     u32x2 e_next = {0u, 0u}; uint32_t m_next = 0;           // meta: base | first << 16 | cnt << 20 | BK_VALID
     u32x2 pv0 = {0u, 0u}, pv1 = pv0, pv2 = pv0, pv3 = pv0, pv4 = pv0, pv5 = pv0, pv6 = pv0, pv7 = pv0;
     uint32_t m_prev = 0; u32x2* sfs_prev = b.sfs;
@@ -236,26 +225,9 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
 #else
         if (m_prev & BK_VALID) {
 #endif
-            u32x2* dst = sfs_prev + (m_prev & 0xffffu);
-            const uint32_t pf = (m_prev >> 16) & 15u, pc = (m_prev >> 20) & 15u;
-            if (pc == 8u) {
-                const u32x4 q0 = {pv0.x, pv0.y, pv1.x, pv1.y}, q1 = {pv2.x, pv2.y, pv3.x, pv3.y};
-                const u32x4 q2 = {pv4.x, pv4.y, pv5.x, pv5.y}, q3 = {pv6.x, pv6.y, pv7.x, pv7.y};
-                bk_store_quad((u32x4*)dst, q0); bk_store_quad((u32x4*)(dst + 2), q1);
-                bk_store_quad((u32x4*)(dst + 4), q2); bk_store_quad((u32x4*)(dst + 6), q3);
-            } else {
-                if (((0u - pf) & 15u) < pc) bk_store_pair(dst + 0, pv0);
-                if (((1u - pf) & 15u) < pc) bk_store_pair(dst + 1, pv1);
-                if (((2u - pf) & 15u) < pc) bk_store_pair(dst + 2, pv2);
-                if (((3u - pf) & 15u) < pc) bk_store_pair(dst + 3, pv3);
-                if (((4u - pf) & 15u) < pc) bk_store_pair(dst + 4, pv4);
-                if (((5u - pf) & 15u) < pc) bk_store_pair(dst + 5, pv5);
-                if (((6u - pf) & 15u) < pc) bk_store_pair(dst + 6, pv6);
-                if (((7u - pf) & 15u) < pc) bk_store_pair(dst + 7, pv7);
-            }
+            bk_store_group(sfs_prev, m_prev, pv0, pv1, pv2, pv3, pv4, pv5, pv6, pv7);
         }
-        // 2. the next group of the run is requested (every lane issues exactly one load, from a harmless address if it has nothing
-        //    to fetch), the next run of the bucket taken when this one is used up
+        // 2. the next group of the run is requested, the next run taken
         {
             const bool adv = has_task && left == 0u, more = run_i < nruns;
             const uint32_t d = mydesc[run_i & 7u];
@@ -279,8 +251,7 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
             BK_BYTE(0u, e.x, pv0) BK_BYTE(1u, e.x, pv1) BK_BYTE(2u, e.x, pv2) BK_BYTE(3u, e.x, pv3)
             BK_BYTE(4u, e.y, pv4) BK_BYTE(5u, e.y, pv5) BK_BYTE(6u, e.y, pv6) BK_BYTE(7u, e.y, pv7)
         }
-        // 4. a lane whose bucket is finished -- the group coded above was its last: nothing of it is still to be requested or
-        //    coded, only the pairs of that group wait for step 1 (with sfs_prev) -- takes its prefetched task
+        // 4. a finished lane takes its prefetched task
         if (!has_task && !(m_next & BK_VALID) && nt_stage == 3u) {
             BK_OPAQUE(nd0); BK_OPAQUE(nd1);
             uint32_t n = 0;
@@ -288,7 +259,7 @@ __global__ __launch_bounds__(64) void bucket_chain_kernel(const BucketBatch b) {
 #pragma unroll
             for (uint32_t j = 0; j < 8u; ++j) if (dsc[j] >> 16) { mydesc[n] = dsc[j] + j * BK_PIECE; ++n; }   // first slot + piece base < 65536
             nruns = n; run_i = 0u;
-            for (uint32_t r = 0; r < 17u; ++r) { *(u32x4*)(my + 8u * r) = def0; *(u32x4*)(my + 8u * r + 4u) = def1; }
+            bk_rows_reset(my, 17u);
             cur_sfs = b.sfs + (size_t)(nt_tid >> 8) * pl; cur_sorted = b.sorted + (size_t)(nt_tid >> 8) * pl;
             left = 0u; has_task = true; nt_stage = 0u;
         }

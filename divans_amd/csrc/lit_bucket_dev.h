@@ -1,4 +1,8 @@
-// lit_bucket_dev.h -- device helpers shared by the bucketed encoder passes (lit_bucket.hip, lit_bucket_mix.hip).
+// lit_bucket_dev.h -- device code shared by the bucketed encoder passes (lit_bucket.hip, lit_bucket_mix.hip): the sort kernels'
+// piece load and segment walk, the arithmetic of one nibble against a packed row, the chain kernels' group
+// store and row reset, and bk_chain_loop -- the loop of a chain kernel (task window, task prefetch, run cursor, delayed stores) that
+// both mix_chain_kernel<MODEL> instances fill with their per-position work; bucket_chain_kernel (lit_bucket.hip) holds the same loop
+// as its own text, see there.
 #ifndef DIVANS_LIT_BUCKET_DEV_H_
 #define DIVANS_LIT_BUCKET_DEV_H_
 #include "lit_device.h"
@@ -7,10 +11,6 @@ namespace divans_hip {
 
 constexpr uint32_t BK_PIECE = 8192;          // positions sorted together
 constexpr uint32_t BK_SORT_THREADS = 256;
-constexpr uint32_t BK_LANE_DWORDS = 148;     // 17 rows x 8 dwords + 8 descriptors, padded: 16-byte aligned and the
-                                             // 64 lanes' b128 accesses at equal offsets cover all 32 banks
-constexpr uint32_t BK_DESC_DW = 136;
-constexpr uint32_t BK_TAB_DW = 64 * BK_LANE_DWORDS;
 constexpr uint32_t BK_VALID = 1u << 31;
 constexpr uint32_t BK_WINDOW = 256;          // tasks a wave reserves per atomic
 constexpr uint32_t BK_CLASSES = 6;           // task lists by bucket size, longest first (a bucket is a serial chain: the long ones must start early)
@@ -38,6 +38,20 @@ struct BkTaskLists {
 
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// the piece's n bytes once into LDS at piece_in + 16 (the bytes before the piece go in front of them), 16 bytes per lane where
+// alignment allows
+__device__ __forceinline__ void bk_load_piece(uint8_t* piece_in, const uint8_t* src, uint32_t n) {
+    const uint32_t tid = threadIdx.x;
+    if ((((uintptr_t)src) & 15u) == 0u) {
+        for (uint32_t i = tid * 16u; i < n; i += BK_SORT_THREADS * 16u) {
+            if (i + 16u <= n) *(u32x4*)(piece_in + 16u + i) = *(const u32x4*)(src + i);
+            else for (uint32_t k = i; k < n; ++k) piece_in[16u + k] = src[k];
+        }
+    } else {
+        for (uint32_t i = tid; i < n; i += BK_SORT_THREADS) piece_in[16u + i] = src[i];
+    }
 }
 
 // The SEG = true sort kernels: the whole workgroup (BK_SORT_THREADS lanes) walks the segment list of ITS stream, 256 segments per
@@ -129,6 +143,173 @@ __device__ __forceinline__ void bk_store_pair(u32x2* p, u32x2 v) {
 __device__ __forceinline__ void bk_store_word(uint32_t* p, uint32_t v) {
     asm volatile("global_store_dword %0, %1, off" : : "v"(p), "v"(v) : "memory");
 }
+
+
+// a fresh CDF row (entry i = 4 (i + 1)) into each of the `nrows` rows at `rows`
+__device__ __forceinline__ void bk_rows_reset(uint32_t* rows, uint32_t nrows) {
+    const u32x4 def0 = {4u | (8u << 16), 12u | (16u << 16), 20u | (24u << 16), 28u | (32u << 16)};
+    const u32x4 def1 = {36u | (40u << 16), 44u | (48u << 16), 52u | (56u << 16), 60u | (64u << 16)};
+    for (uint32_t r = 0; r < nrows; ++r) { *(u32x4*)(rows + 8u * r) = def0; *(u32x4*)(rows + 8u * r + 4u) = def1; }
+}
+
+// The eight values r0 .. r7 of the group `m` describes (base | first << 16 | cnt << 20) leave for plane[base ..]: a full group as
+// 16-byte stores, otherwise the positions the run owns one by one.  T = u32x2 (pairs) or uint32_t (words).
+__device__ __forceinline__ void bk_store_one(u32x2* p, u32x2 v) { bk_store_pair(p, v); }
+__device__ __forceinline__ void bk_store_one(uint32_t* p, uint32_t v) { bk_store_word(p, v); }
+__device__ __forceinline__ void bk_store_full(u32x2* dst, u32x2 r0, u32x2 r1, u32x2 r2, u32x2 r3, u32x2 r4, u32x2 r5, u32x2 r6, u32x2 r7) {
+    const u32x4 q0 = {r0.x, r0.y, r1.x, r1.y}, q1 = {r2.x, r2.y, r3.x, r3.y};
+    const u32x4 q2 = {r4.x, r4.y, r5.x, r5.y}, q3 = {r6.x, r6.y, r7.x, r7.y};
+    bk_store_quad((u32x4*)dst, q0); bk_store_quad((u32x4*)(dst + 2), q1);
+    bk_store_quad((u32x4*)(dst + 4), q2); bk_store_quad((u32x4*)(dst + 6), q3);
+}
+__device__ __forceinline__ void bk_store_full(uint32_t* dst, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t r4, uint32_t r5, uint32_t r6, uint32_t r7) {
+    const u32x4 q0 = {r0, r1, r2, r3}, q1 = {r4, r5, r6, r7};
+    bk_store_quad((u32x4*)dst, q0); bk_store_quad((u32x4*)(dst + 4), q1);
+}
+template <class T>
+__device__ __forceinline__ void bk_store_group(T* plane, uint32_t m, T r0, T r1, T r2, T r3, T r4, T r5, T r6, T r7) {
+    T* dst = plane + (m & 0xffffu);
+    const uint32_t pf = (m >> 16) & 15u, pc = (m >> 20) & 15u;
+    if (pc == 8u) {
+        bk_store_full(dst, r0, r1, r2, r3, r4, r5, r6, r7);
+    } else {
+        if (((0u - pf) & 15u) < pc) bk_store_one(dst + 0, r0);
+        if (((1u - pf) & 15u) < pc) bk_store_one(dst + 1, r1);
+        if (((2u - pf) & 15u) < pc) bk_store_one(dst + 2, r2);
+        if (((3u - pf) & 15u) < pc) bk_store_one(dst + 3, r3);
+        if (((4u - pf) & 15u) < pc) bk_store_one(dst + 4, r4);
+        if (((5u - pf) & 15u) < pc) bk_store_one(dst + 5, r5);
+        if (((6u - pf) & 15u) < pc) bk_store_one(dst + 6, r6);
+        if (((7u - pf) & 15u) < pc) bk_store_one(dst + 7, r7);
+    }
+}
+
+#define BK_OPAQUE(X) asm volatile("" : "+v"(X))     // the compiler knows nothing about X before this point (undefined again below the loop)
+
+// The loop of a chain kernel: ONE LANE per bucket walks the bucket's positions in order with the bucket's rows in LDS.  `b` is the
+// kernel's batch (the fields BucketBatch and MixBucketBatch share: n_streams, slot, sorted, desc, tasks, counters); K is the kernel's
+// own part, a type without state:
+//   K::Group                 u32x2 / u32x4: the eight sorted payloads one load brings (b.sorted holds bytes / 16-bit payloads)
+//   K::ROWS, K::Env          env.my = the lane's LDS: ROWS rows of 8 dwords, then the bucket's 8 run descriptors; the rest is K's
+//   K::Slot, K::slot(b, off) where a bucket's values go: the planes of the stream whose slot starts `off` elements in
+//   K::Out, K::code(...)     what the positions [first, first + cnt) of group e leave once they are blended into the rows
+//   K::store(slot, m, out)   stores it where m says (bk_store_group)
+//
+// A bucket is up to eight runs of consecutive sorted slots, one per 8 KiB piece that holds some of its positions; the task's
+// descriptors are compacted to the non-empty ones when the lane takes it (mydesc[0 .. nruns)).
+// The chain is bound by the vector-memory path, not by its arithmetic (profiles/r03c_chain_role_experiment.txt), so a lane moves
+// its payloads eight at a time: ONE aligned load per iteration covers the sorted slots [base, base + 8), of which the run owns
+// [first, first + cnt); it is requested one iteration before it is coded.  What a group leaves goes out at the top of the NEXT
+// iteration -- 16-byte stores for a full group -- through inline asm: the compiler then sees one load per iteration and waits
+// for it with vmcnt(0) at a point where the only other operations in flight are stores a whole iteration old (a store is
+// acknowledged out of order with loads, so no smaller count would prove the load complete).
+// Every statement below is where it is on purpose (the opacity points, the step order 1-2-3-4, the prefetch one stage per iteration).
+// Everything comes and goes BY VALUE, so that the compiler simplifies this loop over plain values as it would inside a kernel body.
+// bucket_chain_kernel (lit_bucket.hip) holds the same loop as its own text, see there: change the two together.
+template <class K, class Batch>
+__device__ __forceinline__ void bk_chain_loop(const typename K::Env env, const Batch b) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t* my = env.my;
+    uint32_t* mydesc = my + 8u * K::ROWS;
+    const size_t pl = b.slot;
+    const uint32_t cap = b.n_streams * 256u;
+    BkTaskLists lists; lists.load(b.counters);
+    const uint32_t total = lists.total();
+
+    // per-lane chain state
+    bool has_task = false, exhausted = false;
+    uint32_t run_i = 0, nruns = 0, left = 0, idx = 0;
+    typename K::Slot cur = K::slot(b, 0u); const auto* cur_sorted = b.sorted;          // the current bucket's stream slot
+    uint32_t nt_stage = 0, nt_tid = 0;
+    u32x4 nd0 = {0u, 0u, 0u, 0u}, nd1 = {0u, 0u, 0u, 0u};
+    // wave-uniform task window
+    uint32_t win_cur = 0, win_end = 0, nxt_val = 0, nxt_w = 0;
+    const uint32_t long_end = lists.ends[3];     // tasks of at least 2048 positions come first
+    bool nxt_pending = false, drained = false;
+    typename K::Group e_next = {}; uint32_t m_next = 0;     // meta: base | first << 16 | cnt << 20 | BK_VALID
+    typename K::Out out = {};
+    uint32_t m_prev = 0; typename K::Slot prev = cur;
+
+    for (;;) {
+        typename K::Group e = e_next; const uint32_t m = m_next;
+        // 1. what the previous group left goes out (its registers are free again below)
+        if (m_prev & BK_VALID) K::store(prev, m_prev, out);
+        // 2. the next group of the run is requested (every lane issues exactly one load, from a harmless address if it has nothing
+        //    to fetch), the next run of the bucket taken when this one is used up
+        {
+            const bool adv = has_task && left == 0u, more = run_i < nruns;
+            const uint32_t d = mydesc[run_i & 7u];
+            if (adv && more) { left = d >> 16; idx = d & 0xffffu; ++run_i; }
+            if (adv && !more) has_task = false;
+        }
+        {
+            const bool fetch_ = has_task && left != 0u;
+            const uint32_t base = idx & ~7u, first_ = idx & 7u;
+            const uint32_t cnt_ = left < 8u - first_ ? left : 8u - first_;
+            const auto* lp = fetch_ ? cur_sorted + base : b.sorted;
+            e_next = *(const typename K::Group*)lp;
+            m_next = fetch_ ? (base | (first_ << 16) | (cnt_ << 20) | BK_VALID) : 0u;
+            idx += fetch_ ? cnt_ : 0u; left -= fetch_ ? cnt_ : 0u;
+        }
+        // 3. this iteration's group
+        BK_OPAQUE(e);      /* keeps the compiler from touching the payloads (and waiting for them) before this point */
+        m_prev = m; prev = cur;
+        if (m & BK_VALID) out = K::code(env, e, (m >> 16) & 15u, (m >> 20) & 15u, out);
+        // 4. a lane whose bucket is finished -- the group coded above was its last: nothing of it is still to be requested or
+        //    coded, only what that group left waits for step 1 (with `prev`) -- takes its prefetched task
+        if (!has_task && !(m_next & BK_VALID) && nt_stage == 3u) {
+            BK_OPAQUE(nd0); BK_OPAQUE(nd1);
+            uint32_t n = 0;
+            const uint32_t dsc[8] = {nd0.x, nd0.y, nd0.z, nd0.w, nd1.x, nd1.y, nd1.z, nd1.w};
+#pragma unroll
+            for (uint32_t j = 0; j < 8u; ++j) if (dsc[j] >> 16) { mydesc[n] = dsc[j] + j * BK_PIECE; ++n; }   // first slot + piece base < 65536
+            nruns = n; run_i = 0u;
+            bk_rows_reset(my, K::ROWS);
+            const size_t off = (size_t)(nt_tid >> 8) * pl;
+            cur = K::slot(b, off); cur_sorted = b.sorted + off;
+            left = 0u; has_task = true; nt_stage = 0u;
+        }
+        // task prefetch pipeline, one stage per iteration so that no load is waited for in the iteration that issued it
+        const bool want = nt_stage == 0u && !exhausted;
+        if (nt_stage == 2u) nt_stage = 3u;
+        else if (nt_stage == 1u) {
+            BK_OPAQUE(nt_tid);
+            const u32x4* dp = (const u32x4*)(b.desc + (size_t)nt_tid * 8u);
+            nd0 = dp[0]; nd1 = dp[1];
+            nt_stage = 2u;
+        }
+        const unsigned long long wm = __ballot(want);
+        if (wm) {
+            if (win_cur == win_end && nxt_pending) {
+                BK_OPAQUE(nxt_val);
+                const uint32_t basev = (uint32_t)__builtin_amdgcn_readfirstlane((int)nxt_val);
+                nxt_pending = false;
+                if (basev >= total) { drained = true; win_cur = win_end = total; }
+                else { win_cur = basev; win_end = basev + nxt_w < total ? basev + nxt_w : total; }
+            }
+            const uint32_t avail = win_end - win_cur, asked = (uint32_t)__popcll(wm);
+            const uint32_t rank = lanes_below(wm);
+            if (want) {
+                if (rank < avail) {
+                    const uint32_t t = win_cur + rank;
+                    nt_tid = *lists.at(b.tasks, cap, t);
+                    nt_stage = 1u;
+                } else if (drained) exhausted = true;
+            }
+            win_cur += asked < avail ? asked : avail;
+        }
+        // long buckets are handed out 64 at a time: a wave that reserved 256 of them would run four per lane back to back
+        const uint32_t want_w = win_end < long_end ? 64u : BK_WINDOW;
+        if (!nxt_pending && !drained && win_end - win_cur < want_w / 2u) {
+            nxt_w = want_w;
+            if (lane == 0u) nxt_val = atomicAdd(&b.counters[BK_CLAIM], want_w);
+            nxt_pending = true;
+        }
+        const bool done = !has_task && !(m_next & BK_VALID) && !(m_prev & BK_VALID) && nt_stage == 0u && exhausted;
+        if (__ballot(!done) == 0ull) break;
+    }
+}
+#undef BK_OPAQUE
 
 }  // namespace divans_hip
 #endif

@@ -6,7 +6,7 @@
 //   context model  high nibble: row First[ctx]       low nibble: row Second[hi][ctx]  blended with literal_adaptation[3] / [2]
 // and the weights of the average follow from how well each model did on the symbols before (codec/weights.rs:23-38).
 // A row's CDF depends only on the earlier positions that used the same row -- never on the weights -- so the rows
-// can be walked bucket by bucket exactly as in lit_bucket.hip, once per model:
+// can be walked bucket by bucket exactly as in lit_bucket.hip, once per model (the chain loop of both models is bk_chain_loop, lit_bucket_dev.h):
 //   stride model:  buckets keyed by prev  (up to 8 high rows, one per class of prev_prev that reaches a different ctx, + 16 low rows)
 //   context model: buckets keyed by ctx   (1 high row + 16 low rows)
 // Instead of (start, freq) a chain lane leaves the three raw counts mixing needs per nibble -- cdf[sym], cdf[sym-1], cdf[15] --
@@ -27,7 +27,6 @@ constexpr uint32_t MX_CHAIN_WAVES = 3;
 template <int MODEL> struct MxGeom {
     static constexpr uint32_t NH = MODEL == 0 ? 8u : 1u;            // high-nibble rows of a bucket
     static constexpr uint32_t NR = NH + 16u;
-    static constexpr uint32_t DESC_DW = NR * 8u;
     // rows + 8 descriptors, padded so that the 64 lanes' b128 accesses at equal offsets cover all 32 banks
     static constexpr uint32_t LANE_DW = MODEL == 0 ? 204u : 148u;
     static constexpr uint32_t LDS_BYTES = (64u * LANE_DW + 256u) * 4u;
@@ -66,18 +65,8 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void mix_sort_kernel(const MixBuck
     for (uint32_t i = tid; i < 1024u; i += BK_SORT_THREADS) (&hist[0][0])[i] = 0u;
     lut1c[tid] = b.blob[LIT_BLOB_LUT1CLASS + tid];
     for (uint32_t i = tid; i < 2048u; i += BK_SORT_THREADS) ctxf[i] = b.blob[LIT_BLOB_CTXF + i];
-    {
-        const uint8_t* src = in + base;
-        if ((((uintptr_t)src) & 15u) == 0u) {
-            for (uint32_t i = tid * 16u; i < n; i += BK_SORT_THREADS * 16u) {
-                if (i + 16u <= n) *(u32x4*)(piece_in + 16u + i) = *(const u32x4*)(src + i);
-                else for (uint32_t k = i; k < n; ++k) piece_in[16u + k] = src[k];
-            }
-        } else {
-            for (uint32_t i = tid; i < n; i += BK_SORT_THREADS) piece_in[16u + i] = src[i];
-        }
-        if (tid == 0u) { piece_in[15] = base ? in[base - 1u] : 0u; piece_in[14] = base ? in[base - 2u] : 0u; }   // last_8_literals starts at zero
-    }
+    bk_load_piece(piece_in, in + base, n);
+    if (tid == 0u) { piece_in[15] = base ? in[base - 1u] : 0u; piece_in[14] = base ? in[base - 2u] : 0u; }   // last_8_literals starts at zero
     __syncthreads();
     // classes of prev_prev that reach the same context share a high row: slot = the first such class
     if (MODEL == 0) {
@@ -163,49 +152,25 @@ __global__ __launch_bounds__(BK_SORT_THREADS) void mix_sort_kernel(const MixBuck
 }
 
 // ---------------------------------------------------------------------------------------------
-// 3. chains: one lane per bucket, rows in LDS, raw counts out.  Same skeleton as bucket_chain_kernel (task window,
-//    one 16-byte payload load per iteration, stores hidden from the compiler and delayed by an iteration); see there for why.
+// 3. chains: one lane per bucket, rows in LDS, raw counts out.  The loop is bk_chain_loop (lit_bucket_dev.h, where the reasons for
+//    its shape are), one text for both models; this is mix_chain_kernel's part of it: a group is eight 16-bit payloads (one
+//    16-byte load), a position leaves its {high, low} entries and its two row totals, two planes are stored.
 // ---------------------------------------------------------------------------------------------
-template <int MODEL>
-__global__ __launch_bounds__(64) void mix_chain_kernel(const MixBucketBatch b) {
+template <int MODEL> struct MxChain {
     using G = MxGeom<MODEL>;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds32[];
-    const uint32_t lane = threadIdx.x;
-    uint32_t* my = lds32 + lane * G::LANE_DW;
-    uint32_t* mydesc = my + G::DESC_DW;
-    uint32_t* tabh = lds32 + 64u * G::LANE_DW;
-    uint32_t* tabl = tabh + 128u;
-    const uint32_t inch = (uint32_t)(MODEL == 0 ? b.inc0 : b.inc3), incl = (uint32_t)(MODEL == 0 ? b.inc0 : b.inc2);   // literal.rs:320,354 / :242
-    const int limh = MODEL == 0 ? b.lim0 : b.lim3, liml = MODEL == 0 ? b.lim0 : b.lim2;
-    for (uint32_t i = lane; i < 128u; i += 64u) {
-        tabh[i] = bk_tab_entry(i, inch);
-        tabl[i] = bk_tab_entry(i, incl);
+    typedef u32x4 Group;
+    static constexpr uint32_t ROWS = G::NR;
+    struct Env { uint32_t* my; const uint32_t* tabh; const uint32_t* tabl; int limh, liml; };
+    struct Slot { u32x2* x; uint32_t* m; };
+    struct Out {
+        u32x2 x0, x1, x2, x3, x4, x5, x6, x7;                  // {high, low} entries of the group's positions
+        uint32_t t0, t1, t2, t3, t4, t5, t6, t7;               // their row totals, high | low << 16
+    };
+    static __device__ __forceinline__ Slot slot(const MixBucketBatch& b, size_t off) { return {b.xs[MODEL] + off, b.maxes[MODEL] + off}; }
+    static __device__ __forceinline__ void store(Slot to, uint32_t m, Out o) {
+        bk_store_group(to.x, m, o.x0, o.x1, o.x2, o.x3, o.x4, o.x5, o.x6, o.x7);
+        bk_store_group(to.m, m, o.t0, o.t1, o.t2, o.t3, o.t4, o.t5, o.t6, o.t7);
     }
-    __syncthreads();
-    const size_t pl = b.slot;
-    const uint32_t cap = b.n_streams * 256u;
-    BkTaskLists lists; lists.load(b.counters);
-    const uint32_t total = lists.total();
-    const u32x4 def0 = {4u | (8u << 16), 12u | (16u << 16), 20u | (24u << 16), 28u | (32u << 16)};
-    const u32x4 def1 = {36u | (40u << 16), 44u | (48u << 16), 52u | (56u << 16), 60u | (64u << 16)};
-
-    // Same loop as bucket_chain_kernel (see there): a bucket's runs compacted to the non-empty ones, ONE aligned 16-byte load of
-    // eight sorted payloads per iteration requested an iteration ahead, the records of a group stored at the top of the next one.
-    bool has_task = false, exhausted = false;
-    uint32_t run_i = 0, nruns = 0, left = 0, idx = 0;
-    u32x2* const rec_x = b.xs[MODEL]; uint32_t* const rec_m = b.maxes[MODEL];
-    u32x2* cur_x = rec_x; uint32_t* cur_m = rec_m; const uint16_t* cur_sorted = b.sorted;
-    uint32_t nt_stage = 0, nt_tid = 0;
-    u32x4 nd0 = {0u, 0u, 0u, 0u}, nd1 = {0u, 0u, 0u, 0u};
-    uint32_t win_cur = 0, win_end = 0, nxt_val = 0, nxt_w = 0;
-    const uint32_t long_end = lists.ends[3];     // tasks of at least 2048 positions come first
-    bool nxt_pending = false, drained = false;
-    u32x4 e_next = {0u, 0u, 0u, 0u}; uint32_t m_next = 0;   // meta: base | first << 16 | cnt << 20 | BK_VALID
-    u32x2 x0 = {0u, 0u}, x1 = x0, x2 = x0, x3 = x0, x4 = x0, x5 = x0, x6 = x0, x7 = x0;     // {high, low} entries of the group's positions
-    uint32_t t0 = 0u, t1 = 0u, t2 = 0u, t3 = 0u, t4 = 0u, t5 = 0u, t6 = 0u, t7 = 0u;       // their row totals, high | low << 16
-    uint32_t m_prev = 0; u32x2* x_prev = rec_x; uint32_t* t_prev = rec_m;
-
-#define MX_OPAQUE(X) asm volatile("" : "+v"(X))
 #define MX_POS(K, WORD, RX, RT)                                                                         \
     if (((K - first) & 15u) < cnt) {                                                                    \
         const uint32_t pay = (WORD >> (16u * (K & 1u))) & 0xffffu;                                      \
@@ -221,126 +186,32 @@ __global__ __launch_bounds__(64) void mix_chain_kernel(const MixBucketBatch b) {
         *(u32x4*)rowh = H.w0; *(u32x4*)(rowh + 4) = H.w1; *(u32x4*)rowl = L.w0; *(u32x4*)(rowl + 4) = L.w1; \
         RX = vx; RT = vt;                                                                               \
     }
-#define MX_STORE8(DST, R0, R1, R2, R3, R4, R5, R6, R7)                                                  \
-    {                                                                                                   \
-        u32x2* dst = DST + (m_prev & 0xffffu);                                                          \
-        if (pc == 8u) {                                                                                 \
-            const u32x4 q0 = {R0.x, R0.y, R1.x, R1.y}, q1 = {R2.x, R2.y, R3.x, R3.y};                   \
-            const u32x4 q2 = {R4.x, R4.y, R5.x, R5.y}, q3 = {R6.x, R6.y, R7.x, R7.y};                   \
-            bk_store_quad((u32x4*)dst, q0); bk_store_quad((u32x4*)(dst + 2), q1);                       \
-            bk_store_quad((u32x4*)(dst + 4), q2); bk_store_quad((u32x4*)(dst + 6), q3);                 \
-        } else {                                                                                        \
-            if (((0u - pf) & 15u) < pc) bk_store_pair(dst + 0, R0);                                     \
-            if (((1u - pf) & 15u) < pc) bk_store_pair(dst + 1, R1);                                     \
-            if (((2u - pf) & 15u) < pc) bk_store_pair(dst + 2, R2);                                     \
-            if (((3u - pf) & 15u) < pc) bk_store_pair(dst + 3, R3);                                     \
-            if (((4u - pf) & 15u) < pc) bk_store_pair(dst + 4, R4);                                     \
-            if (((5u - pf) & 15u) < pc) bk_store_pair(dst + 5, R5);                                     \
-            if (((6u - pf) & 15u) < pc) bk_store_pair(dst + 6, R6);                                     \
-            if (((7u - pf) & 15u) < pc) bk_store_pair(dst + 7, R7);                                     \
-        }                                                                                               \
-    }
-#define MX_STORE8W(DST, R0, R1, R2, R3, R4, R5, R6, R7)                                                 \
-    {                                                                                                   \
-        uint32_t* dst = DST + (m_prev & 0xffffu);                                                       \
-        if (pc == 8u) {                                                                                 \
-            const u32x4 q0 = {R0, R1, R2, R3}, q1 = {R4, R5, R6, R7};                                   \
-            bk_store_quad((u32x4*)dst, q0); bk_store_quad((u32x4*)(dst + 4), q1);                       \
-        } else {                                                                                        \
-            if (((0u - pf) & 15u) < pc) bk_store_word(dst + 0, R0);                                     \
-            if (((1u - pf) & 15u) < pc) bk_store_word(dst + 1, R1);                                     \
-            if (((2u - pf) & 15u) < pc) bk_store_word(dst + 2, R2);                                     \
-            if (((3u - pf) & 15u) < pc) bk_store_word(dst + 3, R3);                                     \
-            if (((4u - pf) & 15u) < pc) bk_store_word(dst + 4, R4);                                     \
-            if (((5u - pf) & 15u) < pc) bk_store_word(dst + 5, R5);                                     \
-            if (((6u - pf) & 15u) < pc) bk_store_word(dst + 6, R6);                                     \
-            if (((7u - pf) & 15u) < pc) bk_store_word(dst + 7, R7);                                     \
-        }                                                                                               \
-    }
-
-    for (;;) {
-        u32x4 e = e_next; const uint32_t m = m_next;
-        if (m_prev & BK_VALID) {                        // 1. the previous group's records leave
-            const uint32_t pf = (m_prev >> 16) & 15u, pc = (m_prev >> 20) & 15u;
-            MX_STORE8(x_prev, x0, x1, x2, x3, x4, x5, x6, x7)
-            MX_STORE8W(t_prev, t0, t1, t2, t3, t4, t5, t6, t7)
-        }
-        {                                               // 2. the next group of the run is requested, the next run taken
-            const bool adv = has_task && left == 0u, more = run_i < nruns;
-            const uint32_t d = mydesc[run_i & 7u];
-            if (adv && more) { left = d >> 16; idx = d & 0xffffu; ++run_i; }
-            if (adv && !more) has_task = false;
-        }
-        {
-            const bool fetch_ = has_task && left != 0u;
-            const uint32_t base = idx & ~7u, first_ = idx & 7u;
-            const uint32_t cnt_ = left < 8u - first_ ? left : 8u - first_;
-            const uint16_t* lp = fetch_ ? cur_sorted + base : b.sorted;
-            e_next = *(const u32x4*)lp;
-            m_next = fetch_ ? (base | (first_ << 16) | (cnt_ << 20) | BK_VALID) : 0u;
-            idx += fetch_ ? cnt_ : 0u; left -= fetch_ ? cnt_ : 0u;
-        }
-        MX_OPAQUE(e);                                   // 3. this iteration's group
-        m_prev = m; x_prev = cur_x; t_prev = cur_m;
-        if (m & BK_VALID) {
-            const uint32_t first = (m >> 16) & 15u, cnt = (m >> 20) & 15u;
-            MX_POS(0u, e.x, x0, t0) MX_POS(1u, e.x, x1, t1) MX_POS(2u, e.y, x2, t2) MX_POS(3u, e.y, x3, t3)
-            MX_POS(4u, e.z, x4, t4) MX_POS(5u, e.z, x5, t5) MX_POS(6u, e.w, x6, t6) MX_POS(7u, e.w, x7, t7)
-        }
-        if (!has_task && !(m_next & BK_VALID) && nt_stage == 3u) {   // 4. a finished lane takes its prefetched task
-            MX_OPAQUE(nd0); MX_OPAQUE(nd1);
-            uint32_t n = 0;
-            const uint32_t dsc[8] = {nd0.x, nd0.y, nd0.z, nd0.w, nd1.x, nd1.y, nd1.z, nd1.w};
-#pragma unroll
-            for (uint32_t j = 0; j < 8u; ++j) if (dsc[j] >> 16) { mydesc[n] = dsc[j] + j * BK_PIECE; ++n; }
-            nruns = n; run_i = 0u;
-            for (uint32_t r = 0; r < G::NR; ++r) { *(u32x4*)(my + 8u * r) = def0; *(u32x4*)(my + 8u * r + 4u) = def1; }
-            const size_t slot = (size_t)(nt_tid >> 8) * pl;
-            cur_x = rec_x + slot; cur_m = rec_m + slot; cur_sorted = b.sorted + slot;
-            left = 0u; has_task = true; nt_stage = 0u;
-        }
-        const bool want = nt_stage == 0u && !exhausted;
-        if (nt_stage == 2u) nt_stage = 3u;
-        else if (nt_stage == 1u) {
-            MX_OPAQUE(nt_tid);
-            const u32x4* dp = (const u32x4*)(b.desc + (size_t)nt_tid * 8u);
-            nd0 = dp[0]; nd1 = dp[1];
-            nt_stage = 2u;
-        }
-        const unsigned long long wm = __ballot(want);
-        if (wm) {
-            if (win_cur == win_end && nxt_pending) {
-                MX_OPAQUE(nxt_val);
-                const uint32_t basev = (uint32_t)__builtin_amdgcn_readfirstlane((int)nxt_val);
-                nxt_pending = false;
-                if (basev >= total) { drained = true; win_cur = win_end = total; }
-                else { win_cur = basev; win_end = basev + nxt_w < total ? basev + nxt_w : total; }
-            }
-            const uint32_t avail = win_end - win_cur, asked = (uint32_t)__popcll(wm);
-            const uint32_t rank = lanes_below(wm);
-            if (want) {
-                if (rank < avail) {
-                    const uint32_t t = win_cur + rank;
-                    nt_tid = *lists.at(b.tasks, cap, t);
-                    nt_stage = 1u;
-                } else if (drained) exhausted = true;
-            }
-            win_cur += asked < avail ? asked : avail;
-        }
-        // long buckets are handed out 64 at a time: a wave that reserved 256 of them would run four per lane back to back
-        const uint32_t want_w = win_end < long_end ? 64u : BK_WINDOW;
-        if (!nxt_pending && !drained && win_end - win_cur < want_w / 2u) {
-            nxt_w = want_w;
-            if (lane == 0u) nxt_val = atomicAdd(&b.counters[BK_CLAIM], want_w);
-            nxt_pending = true;
-        }
-        const bool done = !has_task && !(m_next & BK_VALID) && !(m_prev & BK_VALID) && nt_stage == 0u && exhausted;
-        if (__ballot(!done) == 0ull) break;
+    static __device__ __forceinline__ Out code(const Env v, const u32x4 e, const uint32_t first, const uint32_t cnt, Out o) {
+        uint32_t* const my = v.my; const uint32_t* const tabh = v.tabh; const uint32_t* const tabl = v.tabl; const int limh = v.limh, liml = v.liml;
+        MX_POS(0u, e.x, o.x0, o.t0) MX_POS(1u, e.x, o.x1, o.t1) MX_POS(2u, e.y, o.x2, o.t2) MX_POS(3u, e.y, o.x3, o.t3)
+        MX_POS(4u, e.z, o.x4, o.t4) MX_POS(5u, e.z, o.x5, o.t5) MX_POS(6u, e.w, o.x6, o.t6) MX_POS(7u, e.w, o.x7, o.t7)
+        return o;
     }
 #undef MX_POS
-#undef MX_STORE8
-#undef MX_STORE8W
-#undef MX_OPAQUE
+};
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void mix_chain_kernel(const MixBucketBatch b) {
+    using G = MxGeom<MODEL>;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds32[];
+    const uint32_t lane = threadIdx.x;
+    uint32_t* my = lds32 + lane * G::LANE_DW;
+    uint32_t* tabh = lds32 + 64u * G::LANE_DW;
+    uint32_t* tabl = tabh + 128u;
+    const uint32_t inch = (uint32_t)(MODEL == 0 ? b.inc0 : b.inc3), incl = (uint32_t)(MODEL == 0 ? b.inc0 : b.inc2);   // literal.rs:320,354 / :242
+    const int limh = MODEL == 0 ? b.lim0 : b.lim3, liml = MODEL == 0 ? b.lim0 : b.lim2;
+    for (uint32_t i = lane; i < 128u; i += 64u) {
+        tabh[i] = bk_tab_entry(i, inch);
+        tabl[i] = bk_tab_entry(i, incl);
+    }
+    __syncthreads();
+    const typename MxChain<MODEL>::Env env = {my, tabh, tabl, limh, liml};
+    bk_chain_loop<MxChain<MODEL>>(env, b);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -481,11 +352,9 @@ __global__ __launch_bounds__(64) void cdf_ops_selftest_bucket_kernel(const u32x4
     __shared__ __attribute__((aligned(16))) uint32_t rows[2][8];
     __shared__ __attribute__((aligned(16))) uint32_t tab[128];
     const uint32_t lane = threadIdx.x;
-    const u32x4 def0 = {4u | (8u << 16), 12u | (16u << 16), 20u | (24u << 16), 28u | (32u << 16)};
-    const u32x4 def1 = {36u | (40u << 16), 44u | (48u << 16), 52u | (56u << 16), 60u | (64u << 16)};
     uint32_t tab_inc = 0u;
     for (uint32_t i = lane; i < 128u; i += 64u) tab[i] = bk_tab_entry(i, tab_inc);
-    if (lane == 0u) for (uint32_t r = 0; r < 2u; ++r) { *(u32x4*)rows[r] = def0; *(u32x4*)(rows[r] + 4) = def1; }
+    if (lane == 0u) bk_rows_reset(rows[0], 2u);
     __syncthreads();
     Weights w; w.w0 = 1; w.w1 = 1; w.norm = 1 << 14;
     for (uint32_t k = 0; k < n; ++k) {
@@ -528,7 +397,7 @@ __global__ __launch_bounds__(64) void cdf_ops_selftest_bucket_kernel(const u32x4
                 const uint32_t sf = bk_pack(R, s);
                 rec[0] = (int)(sf & 0xffffu); rec[1] = (int)(sf >> 16); rec[2] = (int)s;
             } else if (kind == 6u) {
-                for (uint32_t r = 0; r < 2u; ++r) { *(u32x4*)rows[r] = def0; *(u32x4*)(rows[r] + 4) = def1; }
+                bk_rows_reset(rows[0], 2u);
                 for (int i = 0; i < 16; ++i) rec[i] = r0[i];
             } else if (kind == 8u && op.y < 2u) {
                 ((uint16_t*)rows[op.y])[op.z & 15u] = (uint16_t)op.w;
