@@ -396,8 +396,9 @@ class LiteralCodec:
         _check(self._lib.divans_gpu_codec_set_geometry(self._h, int(blocks), cr), "set_geometry")
 
     def set_encode_path(self, path):
-        """0 automatic, 1 streaming model kernel, 2 bucketed model pass (mixing value 4 everywhere, streams <= 64 KiB).  Calls with a
-        segment list take the bucketed pass only under 2; under 0 they keep the streaming kernels."""
+        """0 automatic, 1 streaming model kernel, 2 bucketed model pass (mixing value 4 everywhere, or mixing value 0 everywhere with a
+        context map that is not constant; streams <= 64 KiB).  Calls with a segment list take the bucketed pass only under 2;
+        under 0 they keep the streaming kernels."""
         _check(self._lib.divans_gpu_codec_set_encode_path(self._h, int(path)), "set_encode_path")
 
     def last_encode_path(self):

@@ -164,12 +164,13 @@ struct divans_gpu_codec {
     // bucketed encoder model pass (lit_bucket.hip)
     bool bucket_ok = false;       // the configuration allows it: order-1 rows (see configure_from_geometry), no mixing, streams <= 64 KiB
     bool bucket_mix_ok = false;   // two-model configuration the bucketed pass of lit_bucket_mix.hip covers
+    bool bucket_ctx_ok = false, bucket_ctx_mix_ok = false;   // context-keyed rows (every mixing value 0), one model / two: lit_bucket_ctx.hip
     uint32_t bucket_mix_batch = 32768;   // streams per launch sequence of the bucketed passes (work arrays are sized for this many)
     uint8_t* d_slots = nullptr; size_t slots_bytes = 0;      // divans_gpu_lit_encode_packed: right-aligned output slots of ONE sub-batch
     uint64_t* d_slot_off = nullptr; size_t slot_off_cap = 0;
     std::vector<hipEvent_t> ev_span; size_t enc_spans = 0;   // ... and its events: per sub-batch (start, before the pack, end)
     float last_pack_ms = 0;
-    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
+    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok / bucket_mix_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
     uint32_t last_encode_path = 0;   // the model pass of the last encode / model call: 1 streaming, 2 bucketed, 3 bucketed two-model (0: none yet)
     uint8_t* d_bk = nullptr;      size_t bk_bytes = 0; uint32_t bk_streams = 0;
     uint8_t* d_rs = nullptr;      size_t rs_bytes = 0;
@@ -584,6 +585,11 @@ static void configure_from_geometry(divans_gpu_codec* c) {
     c->bucket_ok = !c->mix && c->geom.mm_uniform == 4 && ctx_from_prev && c->max_stream_len <= 65536u;
     // both models' rows depend on (prev, ctx, high nibble) only when every mixing value is 4 (stride 1, literal.rs:184-192)
     c->bucket_mix_ok = c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes == 1u && c->max_stream_len <= 65536u;
+    // every mixing value 0: all rows of a position -- of both models -- are a function of its context (literal.rs:176-208), whatever
+    // the block types; a constant context would be one bucket per stream and keeps the streaming kernel
+    const bool ctx_keyed = c->geom.mm_uniform == 0 && c->geom.ctx_const < 0 && c->max_stream_len <= 65536u && !c->geom.wrap_check;
+    c->bucket_ctx_ok = !c->mix && ctx_keyed;
+    c->bucket_ctx_mix_ok = c->mix && ctx_keyed;
 }
 
 extern "C" void divans_gpu_codec_destroy(divans_gpu_codec* c);
@@ -656,6 +662,11 @@ static uint32_t bucket_pieces(const divans_gpu_codec* c) { return (c->max_stream
 constexpr uint32_t BUCKET_SLOT_PAD = 0;
 static uint32_t bucket_slot(const divans_gpu_codec* c) { return bucket_pieces(c) * 8192u + BUCKET_SLOT_PAD; }
 static bool use_bucket_mix(const divans_gpu_codec* c) { return c->bucket_mix_ok && c->encode_path != 1u && !c->geom.wrap_check; }
+// the context-keyed passes: on request, and what "automatic" picks for calls without a segment list (the rule the mixing-value-4 passes have:
+// ahead of the streaming kernels at 16 384 and at 64 streams); the flags already exclude wrap_check
+static bool use_bucket_ctx(const divans_gpu_codec* c, bool has_segs) {
+    return (c->bucket_ctx_ok || c->bucket_ctx_mix_ok) && (c->encode_path == 2u || (c->encode_path == 0u && !has_segs));
+}
 static bool use_bucket(const divans_gpu_codec* c) { return c->bucket_ok && c->encode_path != 1u && !c->geom.wrap_check; }   // task ids are stream * 256 + byte in 32 bits: callers keep n_streams < 2^24
 
 // The bucketed passes' work arrays are one allocation (c->d_bk) that only grows; each pass carves it in its own order.
@@ -758,8 +769,10 @@ extern "C" int divans_gpu_codec_set_block_types(divans_gpu_codec* c, uint32_t n_
 extern "C" int divans_gpu_codec_set_encode_path(divans_gpu_codec* c, uint32_t path) {
     if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
     if (path > 2u) return fail(DIVANS_GPU_EINVAL, "path must be 0 (automatic), 1 (streaming) or 2 (bucketed)");
-    if (path == 2u && !c->bucket_ok && !c->bucket_mix_ok)
-        return fail(DIVANS_GPU_EINVAL, "the bucketed encoder needs mixing value 4 everywhere, streams of at most 65536 bytes and either no context map and no mixing or dynamic mixing with one literal block type");
+    if (path == 2u && !c->bucket_ok && !c->bucket_mix_ok && !c->bucket_ctx_ok && !c->bucket_ctx_mix_ok)
+        return fail(DIVANS_GPU_EINVAL, "the bucketed encoder needs streams of at most 65536 bytes and either mixing value 4 everywhere (with no context map and no mixing, or "
+                                       "with dynamic mixing and one literal block type) or mixing value 0 everywhere with a context map that is not constant "
+                                       "(any mixing, up to 8 literal block types, speeds whose row totals stay inside i16)");
     c->encode_path = path;
     return 0;
 }
@@ -1091,6 +1104,36 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
         view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 4u;
         return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
                                   [&](const MixBucketBatch& kk) -> int { HIP_TRY(launch_bucket_mix_model(kk, c->num_cus, c->stream)); return 0; }, after);
+    }
+    if (use_bucket_ctx(c, d_segs != nullptr) && n_streams < (1u << 24)) {
+        // context-keyed rows (lit_bucket_ctx.hip): one sort by context for one model or two; the work arrays of the pass with the same
+        // number of models, sub-batches and status contract as above
+        MixBucketBatch k;
+        std::memset(&k, 0, sizeof(k));
+        uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
+        const bool two = c->bucket_ctx_mix_ok;
+        if (two) {
+            while ((rc = ensure_bucket_mix(c, sub, k)) == DIVANS_GPU_ENOMEM && sub > 1024u) { (void)hipGetLastError(); sub = (sub + 1u) / 2u; }
+            if (rc) return rc;
+        } else {
+            BucketBatch lay;
+            std::memset(&lay, 0, sizeof(lay));
+            rc = ensure_bucket(c, sub, lay); if (rc) return rc;
+            k.counters = lay.counters; k.xs[0] = lay.sfs; k.desc = lay.desc; k.tasks = lay.tasks; k.inv = lay.inv; k.sorted = (uint16_t*)lay.sorted;   // bytes
+        }
+        fill_bucket_batch(c, stream_len, d_segs, k);
+        k.blob = c->d_blob; k.pos_stride = k.slot;
+        k.sf = (uint32_t*)k.xs[0]; k.sf_stride = 2u * k.slot;  // in place: bucket_unsort_kernel / mix_weights_kernel leave the pairs in xs[0]
+        k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
+        c->last_encode_path = two ? 3u : 2u;
+        view.sf = k.sf; view.stride = k.sf_stride;
+        view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * (two ? 4u : 3u);
+        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
+                                  [&](const MixBucketBatch& kk) -> int {
+                                      if (two) HIP_TRY(launch_bucket_ctx_mix_model(kk, c->num_cus, c->stream));
+                                      else HIP_TRY(launch_bucket_ctx_model(kk, c->num_cus * 4u, c->stream));
+                                      return 0;
+                                  }, after);
     }
     rc = ensure_sf(c, n_streams); if (rc) return rc;
     rc = ensure_tables(c); if (rc) return rc;

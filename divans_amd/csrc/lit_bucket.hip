@@ -353,6 +353,10 @@ uint32_t bucket_chain_lds_bytes() { return (64u * BK_LANE_DWORDS + 128u) * 4u; }
 void launch_bucket_tasks(const BucketBatch& b, hipStream_t st) {
     hipLaunchKernelGGL(bucket_tasks_kernel, dim3((b.n_streams + 3u) / 4u), dim3(1024), 0, st, b);
 }
+// step 3 on its own, for the context-keyed pass (lit_bucket_ctx.hip): its buckets have this kernel's 17 rows
+void launch_bucket_chain(const BucketBatch& b, uint32_t chain_blocks, hipStream_t st) {
+    hipLaunchKernelGGL(bucket_chain_kernel, dim3(chain_blocks), dim3(64), bucket_chain_lds_bytes(), st, b);
+}
 void launch_bucket_unsort(const BucketBatch& b, hipStream_t st) {
     hipLaunchKernelGGL(bucket_unsort_kernel, dim3(b.n_streams * b.pieces), dim3(1024), 0, st, b);
 }

@@ -5,6 +5,7 @@
 // as its own text, see there.
 #ifndef DIVANS_LIT_BUCKET_DEV_H_
 #define DIVANS_LIT_BUCKET_DEV_H_
+#include <type_traits>
 #include "lit_device.h"
 
 namespace divans_hip {
@@ -63,6 +64,7 @@ __device__ __forceinline__ void bk_load_piece(uint8_t* piece_in, const uint8_t* 
 // [bt_first, bt_first + n_btypes).  A length is clamped to 65 537 (> any stream of the bucketed passes: the verdict is the same) and
 // the walk stops once the sum has passed the stream's length, so the sum stays far inside 32 bits however long the list is.
 // `wsum` = four words of LDS; every lane of the workgroup must call this (it synchronises).
+// A patch that takes a fourth argument also receives the segment's block type as the list names it (ctx_sort_kernel, lit_bucket_ctx.hip).
 template <class Patch>
 __device__ __forceinline__ void bk_seg_walk(const uint32_t* seg_begin, const LitSegment* segs, uint32_t s, uint32_t len, uint32_t until, bool check,
                                             uint32_t bt_first, uint32_t n_btypes, uint32_t* status, uint32_t* wsum, Patch&& patch) {
@@ -87,7 +89,10 @@ __device__ __forceinline__ void bk_seg_walk(const uint32_t* seg_begin, const Lit
         __syncthreads();
         const uint32_t s0 = wsum[0], s1 = wsum[1], s2 = wsum[2], s3 = wsum[3];
         const uint32_t q = run + (w > 0u ? s0 : 0u) + (w > 1u ? s1 : 0u) + (w > 2u ? s2 : 0u) + incl - l;
-        if (l != 0u && q < len) patch(q, l, ((uint64_t)sg.w << 32) | sg.z);
+        if (l != 0u && q < len) {
+            if constexpr (std::is_invocable_v<Patch&, uint32_t, uint32_t, uint64_t, uint32_t>) patch(q, l, ((uint64_t)sg.w << 32) | sg.z, sg.y);
+            else patch(q, l, ((uint64_t)sg.w << 32) | sg.z);
+        }
         run += s0 + s1 + s2 + s3;
         __syncthreads();
         if (run > len || run >= until) break;

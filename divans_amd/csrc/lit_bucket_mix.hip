@@ -470,4 +470,45 @@ static void launch_mix_sort_seg(int model, const MixBucketBatch& b, hipStream_t 
     else hipLaunchKernelGGL((mix_sort_kernel<1, true>), dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The context-keyed pass (lit_bucket_ctx.hip: every mixing value 0).  Both models' rows are keyed by ctx, so both chain launches
+// walk the buckets of ONE sort with the geometry of the context model (1 high row + 16 low rows):
+//   model 0   high[0][0][ctx], low[0][ctx][hi], both blended with literal_adaptation[0] (literal.rs:320,354), into xs[0] / maxes[0]:
+//             MxChain<1> with the other planes, and the kernel below with the other speeds
+//   model 1   First[ctx], Second[hi][ctx]: mix_chain_kernel<1> as it is
+// The kernel is a template (PLANE = the record planes it fills; 0 is the one instance) so that it is emitted where
+// launch_mix_chain_ctx names it -- behind every other kernel of the file, as the SEG sorts are.
+// ---------------------------------------------------------------------------------------------
+template <int PLANE> struct MxChainCtx : MxChain<1> {
+    static __device__ __forceinline__ Slot slot(const MixBucketBatch& b, size_t off) { return {b.xs[PLANE] + off, b.maxes[PLANE] + off}; }
+};
+
+template <int PLANE>
+__global__ __launch_bounds__(64) void mix_chain_ctx_kernel(const MixBucketBatch b) {
+    using G = MxGeom<1>;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds32[];
+    const uint32_t lane = threadIdx.x;
+    uint32_t* my = lds32 + lane * G::LANE_DW;
+    uint32_t* tabh = lds32 + 64u * G::LANE_DW;
+    uint32_t* tabl = tabh + 128u;
+    for (uint32_t i = lane; i < 128u; i += 64u) {
+        tabh[i] = bk_tab_entry(i, (uint32_t)b.inc0);
+        tabl[i] = tabh[i];
+    }
+    __syncthreads();
+    const typename MxChainCtx<PLANE>::Env env = {my, tabh, tabl, b.lim0, b.lim0};
+    bk_chain_loop<MxChainCtx<PLANE>>(env, b);
+}
+
+void launch_mix_chain_ctx(const MixBucketBatch& b, int model, uint32_t num_cus, hipStream_t st) {
+    if (model == 0) hipLaunchKernelGGL(mix_chain_ctx_kernel<0>, dim3(num_cus * MX_CHAIN_WAVES), dim3(64), MxGeom<1>::LDS_BYTES, st, b);
+    else hipLaunchKernelGGL(mix_chain_kernel<1>, dim3(num_cus * MX_CHAIN_WAVES), dim3(64), MxGeom<1>::LDS_BYTES, st, b);
+}
+
+// the choice launch_bucket_mix_model makes (which keeps its own text: the instances stay where they are in the code object)
+void launch_mix_weights(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st) {
+    if ((b.n_streams + 31u) / 32u > num_cus * 4u) hipLaunchKernelGGL(mix_weights_kernel<2>, dim3((b.n_streams + 31u) / 32u), dim3(64), 0, st, b);
+    else hipLaunchKernelGGL(mix_weights_kernel<1>, dim3((b.n_streams + 31u) / 32u), dim3(64), 0, st, b);
+}
+
 }  // namespace divans_hip

@@ -158,6 +158,19 @@ struct MixBucketBatch {
 };
 hipError_t launch_bucket_mix_model(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st);
 
+// Bucketed encoder model passes for context-keyed rows (lit_bucket_ctx.hip): a context map that is not constant, every reachable
+// mixing value 0, up to LIT_MAX_BTYPES block types, streams <= 64 KiB.  Every row of a position is a function of its context, so one
+// sort by ctx = LIT_BLOB_CTXF[block type of the covering segment][prev][class of prev_prev] (ctx_sort_kernel) serves one model or two.
+// Both take a MixBucketBatch (blob, segment list, speeds):
+//   one model   `sorted` holds bytes (n_streams * slot of them), xs[0] receives the (start | freq << 16) pairs; the other planes are unused
+//   two models  as launch_bucket_mix_model, with 16-bit payloads that hold the byte alone
+hipError_t launch_bucket_ctx_model(const MixBucketBatch& b, uint32_t chain_blocks, hipStream_t st);
+hipError_t launch_bucket_ctx_mix_model(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st);
+// what they borrow from the other two passes' files
+void launch_bucket_chain(const BucketBatch& b, uint32_t chain_blocks, hipStream_t st);                    // bucket_chain_kernel
+void launch_mix_chain_ctx(const MixBucketBatch& b, int model, uint32_t num_cus, hipStream_t st);         // model 0: mix_chain_ctx_kernel<0>, 1: mix_chain_kernel<1>
+void launch_mix_weights(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st);                      // mix_weights_kernel<1 | 2>
+
 uint32_t lit_lds_bytes(const LitBatch& b);
 hipError_t launch_model_encode(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st);
 hipError_t launch_rans_encode(const RansBatch& b, hipStream_t st);

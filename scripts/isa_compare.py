@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Kernel by kernel, the gfx950 assembly of the bucketed encoder passes in this tree against another tree (a checkout of the
+"""Kernel by kernel, the gfx950 assembly of every HIP source of the default build in this tree against another tree (a checkout of the
 parent commit, say): which kernels are instruction for instruction the same, and for every kernel its instruction count, registers,
 LDS, scratch, spills and place in the file.  Cross-compiles only; no GPU.
 
     python scripts/isa_compare.py OTHER_TREE
 
-Both trees' lit_bucket.hip and lit_bucket_mix.hip are compiled with build.py's FLAGS plus -S --cuda-device-only.  Comments and
+Both trees' sources (build.py's SOURCES that end in .hip; one the other tree lacks is listed with its figures) are compiled with
+build.py's FLAGS plus -S --cuda-device-only.  Comments and
 the .file / .ident / .loc lines are dropped; what is left of a kernel's body (instructions, labels, directives) is compared as text.
 The figures come from the kernels' metadata records at the end of the assembly."""
 import os
@@ -19,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from divans_amd import build as dbuild  # noqa: E402
 
-SOURCES = ("lit_bucket.hip", "lit_bucket_mix.hip")
+SOURCES = tuple(s for s in dbuild.SOURCES if s.endswith(".hip"))
 FIELDS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count")
 
 
@@ -75,14 +76,17 @@ def main():
            "(a figure that differs from the other tree's is followed by the other tree's in brackets)", ""]
     with tempfile.TemporaryDirectory() as tmp:
         for src in SOURCES:
-            mine, theirs = kernels(assembly(ROOT, src, tmp, "this")), kernels(assembly(other, src, tmp, "other"))
+            have = os.path.exists(os.path.join(other, "divans_amd", "csrc", src))
+            mine, theirs = kernels(assembly(ROOT, src, tmp, "this")), (kernels(assembly(other, src, tmp, "other")) if have else [])
             nice = demangle([k[0] for k in mine])
             their_place = {k[0]: i for i, k in enumerate(theirs)}
-            out.append(f"{src}: {len(mine)} kernels, {len(theirs)} in the other tree; order " +
-                       ("unchanged" if [k[0] for k in mine] == [k[0] for k in theirs] else "CHANGED"))
+            common = [k[0] for k in mine if k[0] in their_place]
+            out.append(f"{src}: {len(mine)} kernels, {len(theirs)} in the other tree; order of the ones both hold " +
+                       ("unchanged" if common == [k[0] for k in theirs] else "CHANGED") +
+                       f"; identical: {sum(1 for n, b, _ in mine if n in their_place and b == theirs[their_place[n]][1])}")
             for i, (name, body, meta) in enumerate(mine):
                 if name not in their_place:
-                    out.append(f"  {nice[name]:44s} not in the other tree")
+                    out.append(f"  {nice[name]:44s} {'new':9s} | " + " | ".join([str(n_instructions(body))] + [str(meta.get(f)) for f in FIELDS] + [str(i + 1)]))
                     continue
                 j = their_place[name]
                 _, obody, ometa = theirs[j]
