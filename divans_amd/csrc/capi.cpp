@@ -165,12 +165,14 @@ struct divans_gpu_codec {
     bool bucket_ok = false;       // the configuration allows it: order-1 rows (see configure_from_geometry), no mixing, streams <= 64 KiB
     bool bucket_mix_ok = false;   // two-model configuration the bucketed pass of lit_bucket_mix.hip covers
     bool bucket_ctx_ok = false, bucket_ctx_mix_ok = false;   // context-keyed rows (every mixing value 0), one model / two: lit_bucket_ctx.hip
+    bool bucket_mix_bt_ok = false;   // two models, mixing value 4, several block types, at most 8 high rows per previous byte (mix_bt_sort_kernel)
+    uint32_t high_row_slots = 0;     // the most distinct contexts one previous byte reaches over the codec's block types (derive_high_row_slots)
     uint32_t bucket_mix_batch = 32768;   // streams per launch sequence of the bucketed passes (work arrays are sized for this many)
     uint8_t* d_slots = nullptr; size_t slots_bytes = 0;      // divans_gpu_lit_encode_packed: right-aligned output slots of ONE sub-batch
     uint64_t* d_slot_off = nullptr; size_t slot_off_cap = 0;
     std::vector<hipEvent_t> ev_span; size_t enc_spans = 0;   // ... and its events: per sub-batch (start, before the pack, end)
     float last_pack_ms = 0;
-    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok / bucket_mix_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
+    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok / bucket_mix_ok / bucket_ctx*_ok / bucket_mix_bt_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
     uint32_t last_encode_path = 0;   // the model pass of the last encode / model call: 1 streaming, 2 bucketed, 3 bucketed two-model (0: none yet)
     uint8_t* d_bk = nullptr;      size_t bk_bytes = 0; uint32_t bk_streams = 0;
     uint8_t* d_rs = nullptr;      size_t rs_bytes = 0;
@@ -218,6 +220,33 @@ extern "C" int divans_gpu_speed_supported(int32_t inc, int32_t lim) {
 // when encoding, BAD_STREAM (+ the per-stream flag) when decoding.
 extern "C" int divans_gpu_speed_accepted(int32_t inc, int32_t lim) {
     return inc >= 0 && inc <= 0x7fff && lim >= -0x8000 && lim <= 0x7fff;
+}
+
+// The stride model's high-nibble row is [ctx][prev] (literal.rs:205-208, mixing value 4): a bucket keyed by `prev` holds one high row
+// per context `prev` can reach.  slot_of[bt][prev][k] (2048 bytes per block type, laid out like LIT_BLOB_CTXF) = the index of
+// LIT_BLOB_CTXF[bt][prev][k] among the distinct contexts of `prev`, numbered in order of first appearance over (bt, k < lut1_classes);
+// entries k >= lut1_classes copy class 0 as the context table does.  The table goes behind the mixing mask (no other offset of the
+// blob moves; mix_bt_sort_kernel, lit_bucket_ctx.hip, is its only reader).  Returns the largest number of slots any `prev` takes.
+static uint32_t derive_high_row_slots(const LitGeometry& g, std::vector<uint8_t>& blob) {
+    const size_t at = (size_t)g.mix_off + DIVANS_GPU_NUM_MIXING_VALUES;
+    blob.resize(at + (size_t)LIT_CTXF_BYTES * g.n_btypes, 0);
+    uint32_t most = 0;
+    for (uint32_t prev = 0; prev < 256u; ++prev) {
+        uint8_t seen[64]; uint32_t used = 0;      // at most 8 block types x 8 classes
+        for (uint32_t bt = 0; bt < g.n_btypes; ++bt) {
+            const uint8_t* row = &blob[LIT_BLOB_CTXF + LIT_CTXF_BYTES * bt + prev * 8u];
+            uint8_t* out = &blob[at + LIT_CTXF_BYTES * bt + prev * 8u];
+            for (uint32_t k = 0; k < g.lut1_classes; ++k) {
+                uint32_t i = 0;
+                while (i < used && seen[i] != row[k]) ++i;
+                if (i == used) seen[used++] = row[k];
+                out[k] = (uint8_t)i;
+            }
+            for (uint32_t k = g.lut1_classes; k < 8u; ++k) out[k] = out[0];
+        }
+        most = std::max(most, used);
+    }
+    return most;
 }
 
 // Tables are built for the literal block types [bt_first, bt_first + n_btypes): one for a batch of single-segment
@@ -590,6 +619,11 @@ static void configure_from_geometry(divans_gpu_codec* c) {
     const bool ctx_keyed = c->geom.mm_uniform == 0 && c->geom.ctx_const < 0 && c->max_stream_len <= 65536u && !c->geom.wrap_check;
     c->bucket_ctx_ok = !c->mix && ctx_keyed;
     c->bucket_ctx_mix_ok = c->mix && ctx_keyed;
+    // mixing value 4, two models, several block types: the stride rows stay keyed by prev and the block type enters the high-row slot
+    // (derive_high_row_slots); the chain keeps eight high rows per bucket.  A constant context is one bucket per stream for the
+    // context model, as above
+    c->bucket_mix_bt_ok = c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes > 1u && c->geom.ctx_const < 0 && c->high_row_slots <= 8u &&
+                          c->max_stream_len <= 65536u && !c->geom.wrap_check;
 }
 
 extern "C" void divans_gpu_codec_destroy(divans_gpu_codec* c);
@@ -609,11 +643,12 @@ extern "C" int divans_gpu_codec_create(divans_gpu_codec** out, const divans_lit_
     std::vector<uint8_t> blob;
     int rc = derive_geometry(*cfg, cfg->btype, 1, c->geom, blob);
     if (rc) { divans_gpu_codec_destroy(c); return rc; }
+    c->high_row_slots = derive_high_row_slots(c->geom, blob);
     c->mix = cfg->context_mixing > 1;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = (uint32_t)prop.multiProcessorCount;
     configure_from_geometry(c);
-    hipError_t he = hipMalloc(&c->d_blob, LIT_BLOB_MAX_BYTES);
+    hipError_t he = hipMalloc(&c->d_blob, LIT_BLOB_MAX_BYTES + LIT_CTXF_BYTES * LIT_MAX_BTYPES);   // + the high-row slot tables
     if (he == hipSuccess) he = hipMalloc(&c->d_status, 64);
     if (he == hipSuccess) he = hipMalloc(&c->d_rank, 256);
     if (he == hipSuccess) he = hipEventCreate(&c->ps.e0);
@@ -666,6 +701,11 @@ static bool use_bucket_mix(const divans_gpu_codec* c) { return c->bucket_mix_ok 
 // ahead of the streaming kernels at 16 384 and at 64 streams); the flags already exclude wrap_check
 static bool use_bucket_ctx(const divans_gpu_codec* c, bool has_segs) {
     return (c->bucket_ctx_ok || c->bucket_ctx_mix_ok) && (c->encode_path == 2u || (c->encode_path == 0u && !has_segs));
+}
+// mixing value 4, two models, several block types (launch_bucket_mix_bt_model): on request, and what "automatic" picks for calls without
+// a segment list (ahead of the streaming kernels at 16 384 and at 64 streams)
+static bool use_bucket_mix_bt(const divans_gpu_codec* c, bool has_segs) {
+    return c->bucket_mix_bt_ok && (c->encode_path == 2u || (c->encode_path == 0u && !has_segs));
 }
 static bool use_bucket(const divans_gpu_codec* c) { return c->bucket_ok && c->encode_path != 1u && !c->geom.wrap_check; }   // task ids are stream * 256 + byte in 32 bits: callers keep n_streams < 2^24
 
@@ -741,9 +781,10 @@ extern "C" int divans_gpu_codec_set_block_types(divans_gpu_codec* c, uint32_t n_
     HIP_TRY(hipSetDevice(c->device));
     LitGeometry g; std::vector<uint8_t> blob;
     int rc = derive_geometry(c->cfg, 0, n_btypes, g, blob); if (rc) return rc;
+    const uint32_t slots = derive_high_row_slots(g, blob);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    c->geom = g;
+    c->geom = g; c->high_row_slots = slots;
     free_tables(c);
     // the block types change the LDS the context tables take, not what the caller chose before: keep an explicitly set
     // grid / cache organisation / decoder generation, clamped to what still fits the LDS (and to caches the new row count allows)
@@ -769,9 +810,10 @@ extern "C" int divans_gpu_codec_set_block_types(divans_gpu_codec* c, uint32_t n_
 extern "C" int divans_gpu_codec_set_encode_path(divans_gpu_codec* c, uint32_t path) {
     if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
     if (path > 2u) return fail(DIVANS_GPU_EINVAL, "path must be 0 (automatic), 1 (streaming) or 2 (bucketed)");
-    if (path == 2u && !c->bucket_ok && !c->bucket_mix_ok && !c->bucket_ctx_ok && !c->bucket_ctx_mix_ok)
+    if (path == 2u && !c->bucket_ok && !c->bucket_mix_ok && !c->bucket_ctx_ok && !c->bucket_ctx_mix_ok && !c->bucket_mix_bt_ok)
         return fail(DIVANS_GPU_EINVAL, "the bucketed encoder needs streams of at most 65536 bytes and either mixing value 4 everywhere (with no context map and no mixing, or "
-                                       "with dynamic mixing and one literal block type) or mixing value 0 everywhere with a context map that is not constant "
+                                       "with dynamic mixing and one literal block type, or with dynamic mixing and several block types provided that no "
+                                       "previous byte reaches more than eight contexts: divans_gpu_codec_high_row_slots) or mixing value 0 everywhere with a context map that is not constant "
                                        "(any mixing, up to 8 literal block types, speeds whose row totals stay inside i16)");
     c->encode_path = path;
     return 0;
@@ -780,6 +822,12 @@ extern "C" int divans_gpu_codec_set_encode_path(divans_gpu_codec* c, uint32_t pa
 extern "C" int divans_gpu_codec_last_encode_path(divans_gpu_codec* c, uint32_t* path) {
     if (!c || !path) return fail(DIVANS_GPU_EINVAL, "null argument");
     *path = c->last_encode_path;
+    return 0;
+}
+
+extern "C" int divans_gpu_codec_high_row_slots(divans_gpu_codec* c, uint32_t* slots) {
+    if (!c || !slots) return fail(DIVANS_GPU_EINVAL, "null argument");
+    *slots = c->high_row_slots;
     return 0;
 }
 
@@ -1134,6 +1182,24 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
                                       else HIP_TRY(launch_bucket_ctx_model(kk, c->num_cus * 4u, c->stream));
                                       return 0;
                                   }, after);
+    }
+    if (use_bucket_mix_bt(c, d_segs != nullptr) && n_streams < (1u << 24)) {
+        // several block types under mixing value 4 (launch_bucket_mix_bt_model): the two-model pass with the block type in the stride
+        // model's high-row slot and in the context model's key; work arrays, sub-batches and status contract as above
+        MixBucketBatch k;
+        std::memset(&k, 0, sizeof(k));
+        uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
+        while ((rc = ensure_bucket_mix(c, sub, k)) == DIVANS_GPU_ENOMEM && sub > 1024u) { (void)hipGetLastError(); sub = (sub + 1u) / 2u; }
+        if (rc) return rc;
+        fill_bucket_batch(c, stream_len, d_segs, k);
+        k.blob = c->d_blob; k.pos_stride = k.slot;
+        k.sf = (uint32_t*)k.xs[0]; k.sf_stride = 2u * k.slot;
+        k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
+        c->last_encode_path = 3u;
+        view.sf = k.sf; view.stride = k.sf_stride;
+        view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 4u;
+        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
+                                  [&](const MixBucketBatch& kk) -> int { HIP_TRY(launch_bucket_mix_bt_model(kk, c->num_cus, c->stream)); return 0; }, after);
     }
     rc = ensure_sf(c, n_streams); if (rc) return rc;
     rc = ensure_tables(c); if (rc) return rc;

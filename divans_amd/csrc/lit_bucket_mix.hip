@@ -511,4 +511,10 @@ void launch_mix_weights(const MixBucketBatch& b, uint32_t num_cus, hipStream_t s
     else hipLaunchKernelGGL(mix_weights_kernel<1>, dim3((b.n_streams + 31u) / 32u), dim3(64), 0, st, b);
 }
 
+// the chain launches of launch_bucket_mix_model, for the pass that brings its own sorts (launch_bucket_mix_bt_model, lit_bucket_ctx.hip)
+void launch_mix_chain(const MixBucketBatch& b, int model, uint32_t num_cus, hipStream_t st) {
+    if (model == 0) hipLaunchKernelGGL(mix_chain_kernel<0>, dim3(num_cus * MX_CHAIN_WAVES), dim3(64), MxGeom<0>::LDS_BYTES, st, b);
+    else hipLaunchKernelGGL(mix_chain_kernel<1>, dim3(num_cus * MX_CHAIN_WAVES), dim3(64), MxGeom<1>::LDS_BYTES, st, b);
+}
+
 }  // namespace divans_hip

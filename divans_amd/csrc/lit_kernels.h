@@ -171,6 +171,14 @@ void launch_bucket_chain(const BucketBatch& b, uint32_t chain_blocks, hipStream_
 void launch_mix_chain_ctx(const MixBucketBatch& b, int model, uint32_t num_cus, hipStream_t st);         // model 0: mix_chain_ctx_kernel<0>, 1: mix_chain_kernel<1>
 void launch_mix_weights(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st);                      // mix_weights_kernel<1 | 2>
 
+// Bucketed two-model pass for SEVERAL literal block types (lit_bucket_ctx.hip): context map on, every mixing value 4, dynamic mixing,
+// up to LIT_MAX_BTYPES block types of which no previous byte reaches more than eight contexts, streams <= 64 KiB.  The stride model's
+// buckets stay keyed by prev and the block type of the covering segment enters the payload's high-row slot (mix_bt_sort_kernel reads
+// the slot tables the host put behind the mixing mask: blob + LIT_BLOB_CTXF + LIT_CTXF_BYTES * n_btypes + 8192); the context model's
+// sort is ctx_sort_kernel<true, SEG>.  Chains, task lists, unsorts and the Weights walk are launch_bucket_mix_model's.
+hipError_t launch_bucket_mix_bt_model(const MixBucketBatch& b, uint32_t num_cus, hipStream_t st);
+void launch_mix_chain(const MixBucketBatch& b, int model, uint32_t num_cus, hipStream_t st);             // mix_chain_kernel<0 | 1> (lit_bucket_mix.hip)
+
 uint32_t lit_lds_bytes(const LitBatch& b);
 hipError_t launch_model_encode(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st);
 hipError_t launch_rans_encode(const RansBatch& b, hipStream_t st);

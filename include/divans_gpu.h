@@ -239,20 +239,28 @@ int divans_gpu_codec_set_geometry(divans_gpu_codec *c, uint32_t blocks, uint32_t
  * lit_bucket.hip, lit_bucket_mix.hip, lit_bucket_ctx.hip).  The bucketed pass exists for configurations whose every mixing value is 4
  * (stride 1) and streams of at most 65536 bytes: without mixing when the context is constant or follows from the previous
  * byte alone (divans_lit_config_simple; LSB6 / MSB6 prediction modes with any context map, i.e. what the literal-only
- * compressor emits), or with a context map and dynamic mixing for one literal block type (divans_lit_config_context_mixing).  There it is what
+ * compressor emits), or with a context map and dynamic mixing for one literal block type (divans_lit_config_context_mixing) or for several
+ * of which no previous byte reaches more than eight contexts (divans_gpu_codec_high_row_slots).  There it is what
  * "automatic" picks for calls without a segment list.  Both produce the same bytes.
  * It also exists for context-keyed rows (lit_bucket_ctx.hip): every mixing value 0 -- what a stream whose PredictionMode names no
  * mixing values gets -- with a context map that is not constant, without mixing or with dynamic mixing, for any number of literal
  * block types (divans_gpu_codec_set_block_types), streams of at most 65536 bytes and speeds divans_gpu_speed_supported accepts.
  * There, too, it is what "automatic" picks for calls without a segment list.
  * Asking for path 2 elsewhere is DIVANS_GPU_EINVAL: mixing value 0 with a constant context (one bucket per stream), mixing value 4
- * with UTF8 / SIGN and no mixing or with mixing and several block types, strides, table-driven masks, longer streams.
+ * with UTF8 / SIGN and no mixing, or with mixing and several block types of which some previous byte reaches more than eight contexts
+ * (divans_gpu_codec_high_row_slots), strides, table-driven masks, longer streams.
  * A call WITH a segment list (divans_gpu_lit_encode_segments_batch) takes the bucketed pass only under path 2 -- a segment's last8
  * then replaces the bytes before its first position in the bucket keys -- and the streaming kernels under "automatic". */
 int divans_gpu_codec_set_encode_path(divans_gpu_codec *c, uint32_t path);
 /* The model pass the last encode / model call of this codec ran: 0 = none yet, 1 = streaming kernels, 2 = bucketed one-model
  * pass (lit_bucket.hip; context-keyed: lit_bucket_ctx.hip), 3 = bucketed two-model pass (lit_bucket_mix.hip; context-keyed likewise). */
 int divans_gpu_codec_last_encode_path(divans_gpu_codec *c, uint32_t *path);
+/* The most distinct contexts one previous byte reaches over the block types the codec keeps tables for and the classes of the byte
+ * before it (1 for a constant context map, at most 4 / 8 per block type under UTF8 / SIGN): the high-nibble rows a bucket of the
+ * stride model needs.  With mixing value 4 everywhere, dynamic mixing and several block types (divans_gpu_codec_set_block_types(c, n > 1))
+ * path 2 exists where this number is at most 8 -- brotli's clustered context maps stay far below it -- and the codec's context map is
+ * not constant; there, too, it is what "automatic" picks for calls without a segment list, and a list takes it under path 2.  For a codec with one block type the number says how many of the eight rows its buckets use. */
+int divans_gpu_codec_high_row_slots(divans_gpu_codec *c, uint32_t *slots);
 /* Streams the bucketed two-model pass takes per launch sequence (default 32768, halved until its work arrays -- 1.9 MB
  * per 64 KiB stream -- fit the device).  A tuning / test knob: the coded bytes do not depend on it. */
 int divans_gpu_codec_set_bucket_batch(divans_gpu_codec *c, uint32_t streams);
