@@ -162,6 +162,7 @@ def load_library():
     L.divans_gpu_codec_last_encode_path.argtypes = [vp, ctypes.POINTER(u32)]
     L.divans_gpu_codec_set_bucket_batch.argtypes = [vp, u32]
     L.divans_gpu_codec_high_row_slots.argtypes = [vp, ctypes.POINTER(u32)]
+    L.divans_gpu_codec_bucket_stride.argtypes = [vp, ctypes.POINTER(u32)]
     L.divans_gpu_lit_encode_host_pipelined.argtypes = [vp, vp, u32, u32, vp, ctypes.c_size_t, vp, vp, ctypes.POINTER(ctypes.c_size_t), u32]
     L.divans_gpu_lit_decode_host_pipelined.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32]
     L.divans_gpu_host_alloc.argtypes = [ctypes.c_size_t]
@@ -230,7 +231,7 @@ def exported_symbols():
         "divans_gpu_codec_destroy", "divans_gpu_last_error", "divans_gpu_lit_encode_bound",
         "divans_gpu_lit_encode_batch", "divans_gpu_lit_encode_packed", "divans_gpu_lit_decode_batch", "divans_gpu_pack_streams",
         "divans_gpu_lit_encode_host", "divans_gpu_lit_encode_host_chunks", "divans_gpu_lit_decode_host", "divans_gpu_codec_info",
-        "divans_gpu_codec_set_geometry", "divans_gpu_codec_set_split_cache", "divans_gpu_codec_tune_tables", "divans_gpu_codec_search_tables", "divans_gpu_codec_table_placement", "divans_gpu_table_memory", "divans_gpu_set_table_va_cap", "divans_gpu_trim", "divans_gpu_codec_set_decoder", "divans_gpu_experimental_decoders", "divans_gpu_codec_set_byte_order", "divans_gpu_codec_byte_order", "divans_gpu_codec_row_replay", "divans_gpu_codec_set_rans_split", "divans_gpu_codec_set_encode_path", "divans_gpu_codec_last_encode_path", "divans_gpu_codec_set_bucket_batch", "divans_gpu_codec_high_row_slots", "divans_gpu_lit_model_batch",
+        "divans_gpu_codec_set_geometry", "divans_gpu_codec_set_split_cache", "divans_gpu_codec_tune_tables", "divans_gpu_codec_search_tables", "divans_gpu_codec_table_placement", "divans_gpu_table_memory", "divans_gpu_set_table_va_cap", "divans_gpu_trim", "divans_gpu_codec_set_decoder", "divans_gpu_experimental_decoders", "divans_gpu_codec_set_byte_order", "divans_gpu_codec_byte_order", "divans_gpu_codec_row_replay", "divans_gpu_codec_set_rans_split", "divans_gpu_codec_set_encode_path", "divans_gpu_codec_last_encode_path", "divans_gpu_codec_set_bucket_batch", "divans_gpu_codec_high_row_slots", "divans_gpu_codec_bucket_stride", "divans_gpu_lit_model_batch",
         "divans_gpu_selftest_division", "divans_gpu_speed_supported", "divans_gpu_speed_accepted", "divans_gpu_codec_status", "divans_gpu_codec_clear_status", "divans_gpu_codec_status_async", "divans_gpu_codec_last_decode_kernel", "divans_gpu_codec_set_stream_flags", "divans_gpu_codec_set_block_types",
         "divans_gpu_lit_encode_segments_batch", "divans_gpu_lit_decode_segments_batch",
         "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_cdf_ops_on", "divans_gpu_selftest_rans_pairs", "divans_gpu_lit_encode_batch_chunks",
@@ -398,7 +399,8 @@ class LiteralCodec:
 
     def set_encode_path(self, path):
         """0 automatic, 1 streaming model kernel, 2 bucketed model pass (mixing value 4 everywhere -- with several block types: dynamic
-        mixing and high_row_slots() <= 8 --, or mixing value 0 everywhere with a context map that is not constant; streams <= 64 KiB).  Calls with a segment list take the bucketed pass only under 2;
+        mixing and high_row_slots() <= 8 --, or mixing value 0 everywhere with a context map that is not constant, or one stride distance
+        of 2, 3, 4 or 8 everywhere with a constant context and no mixing: bucket_stride(); streams <= 64 KiB).  Calls with a segment list take the bucketed pass only under 2;
         under 0 they keep the streaming kernels."""
         _check(self._lib.divans_gpu_codec_set_encode_path(self._h, int(path)), "set_encode_path")
 
@@ -413,6 +415,13 @@ class LiteralCodec:
         several block types set_encode_path(2) is accepted where this is at most 8"""
         v = ctypes.c_uint32(0)
         _check(self._lib.divans_gpu_codec_high_row_slots(self._h, ctypes.byref(v)), "high_row_slots")
+        return int(v.value)
+
+    def bucket_stride(self):
+        """the distance the bucketed one-model pass keys its buckets by: 1 (mixing value 4), 2 / 3 / 4 / 8 (mixing values 5, 6, 7, and 8
+        and above, under a constant context), or 0 where the codec has no such pass"""
+        v = ctypes.c_uint32(0)
+        _check(self._lib.divans_gpu_codec_bucket_stride(self._h, ctypes.byref(v)), "bucket_stride")
         return int(v.value)
 
     def set_bucket_batch(self, streams):

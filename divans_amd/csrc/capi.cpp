@@ -163,6 +163,8 @@ struct divans_gpu_codec {
     uint32_t* d_status = nullptr;
     // bucketed encoder model pass (lit_bucket.hip)
     bool bucket_ok = false;       // the configuration allows it: order-1 rows (see configure_from_geometry), no mixing, streams <= 64 KiB
+    uint32_t stride_dist = 0;     // the stride distance every reachable mixing value selects (derive_stride_distance), 0: none / not one
+    uint32_t bucket_stride = 0;   // bucket_ok: the distance its buckets are keyed by -- 1, or 2 / 3 / 4 / 8 (bucket_sort_stride_kernel); else 0
     bool bucket_mix_ok = false;   // two-model configuration the bucketed pass of lit_bucket_mix.hip covers
     bool bucket_ctx_ok = false, bucket_ctx_mix_ok = false;   // context-keyed rows (every mixing value 0), one model / two: lit_bucket_ctx.hip
     bool bucket_mix_bt_ok = false;   // two models, mixing value 4, several block types, at most 8 high rows per previous byte (mix_bt_sort_kernel)
@@ -172,7 +174,7 @@ struct divans_gpu_codec {
     uint64_t* d_slot_off = nullptr; size_t slot_off_cap = 0;
     std::vector<hipEvent_t> ev_span; size_t enc_spans = 0;   // ... and its events: per sub-batch (start, before the pack, end)
     float last_pack_ms = 0;
-    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok / bucket_mix_ok / bucket_ctx*_ok / bucket_mix_bt_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
+    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok -- stride 1, or 2 / 3 / 4 / 8 under a constant context -- / bucket_mix_ok / bucket_ctx*_ok / bucket_mix_bt_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
     uint32_t last_encode_path = 0;   // the model pass of the last encode / model call: 1 streaming, 2 bucketed, 3 bucketed two-model (0: none yet)
     uint8_t* d_bk = nullptr;      size_t bk_bytes = 0; uint32_t bk_streams = 0;
     uint8_t* d_rs = nullptr;      size_t rs_bytes = 0;
@@ -247,6 +249,26 @@ static uint32_t derive_high_row_slots(const LitGeometry& g, std::vector<uint8_t>
         most = std::max(most, used);
     }
     return most;
+}
+
+// The stride distance of a configuration: a mixing value v >= 4 takes index_b from the byte 1 + min(7, v ^ 4) places back
+// (literal.rs:192-201: 4, 5, 6, 7 -> 1, 2, 3, 4, everything from 8 up -> 8).  d when every reachable entry of the mixing mask
+// (index = ctx | nibble << 8 | low << 12 over the contexts the tables can produce, as in derive_geometry) is at least 4 and all
+// give the same distance -- a mask that mixes 8 and 12 has distance 8 --, else 0.
+static uint32_t derive_stride_distance(const divans_lit_config& cfg, const LitGeometry& g, const std::vector<uint8_t>& blob) {
+    bool ctx_seen[256] = {false};
+    for (uint32_t bt = 0; bt < g.n_btypes; ++bt)
+        for (uint32_t prev = 0; prev < 256u; ++prev)
+            for (uint32_t k = 0; k < g.lut1_classes; ++k) ctx_seen[blob[LIT_BLOB_CTXF + LIT_CTXF_BYTES * bt + prev * 8u + k]] = true;
+    uint32_t dist = 0;
+    for (int idx = 0; idx < DIVANS_GPU_NUM_MIXING_VALUES; ++idx) {
+        if (!ctx_seen[idx & 0xff]) continue;
+        const uint32_t m = cfg.mixing_mask[idx];
+        if (m < 4u) return 0u;
+        const uint32_t d = 1u + std::min(7u, m ^ 4u);
+        if (dist == 0u) dist = d; else if (d != dist) return 0u;
+    }
+    return dist;
 }
 
 // Tables are built for the literal block types [bt_first, bt_first + n_btypes): one for a batch of single-segment
@@ -612,6 +634,13 @@ static void configure_from_geometry(divans_gpu_codec* c) {
     // class and one block type: LSB6 / MSB6 -- what the reference's literal-only compressor emits, raw_to_cmd/mod.rs:115-140)
     const bool ctx_from_prev = c->geom.ctx_const >= 0 || (c->geom.lut1_classes == 1u && c->geom.n_btypes == 1u);
     c->bucket_ok = !c->mix && c->geom.mm_uniform == 4 && ctx_from_prev && c->max_stream_len <= 65536u;
+    c->bucket_stride = c->bucket_ok ? 1u : 0u;
+    // strides 2, 3, 4 and 8 (mixing values 5, 6, 7, and 8 and above): high row [ctx][b_d], low row [b_d][hi] with b_d the byte d places
+    // back -- under a CONSTANT context a function of b_d alone, the bucket key (bucket_sort_stride_kernel).  A context that follows
+    // from prev (LSB6 / MSB6) would need two key bytes, prev and b_d, and stays on the streaming kernel
+    if (!c->mix && c->stride_dist > 1u && c->geom.ctx_const >= 0 && c->max_stream_len <= 65536u && !c->geom.wrap_check) {
+        c->bucket_ok = true; c->bucket_stride = c->stride_dist;
+    }
     // both models' rows depend on (prev, ctx, high nibble) only when every mixing value is 4 (stride 1, literal.rs:184-192)
     c->bucket_mix_ok = c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes == 1u && c->max_stream_len <= 65536u;
     // every mixing value 0: all rows of a position -- of both models -- are a function of its context (literal.rs:176-208), whatever
@@ -644,6 +673,7 @@ extern "C" int divans_gpu_codec_create(divans_gpu_codec** out, const divans_lit_
     int rc = derive_geometry(*cfg, cfg->btype, 1, c->geom, blob);
     if (rc) { divans_gpu_codec_destroy(c); return rc; }
     c->high_row_slots = derive_high_row_slots(c->geom, blob);
+    c->stride_dist = derive_stride_distance(*cfg, c->geom, blob);
     c->mix = cfg->context_mixing > 1;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = (uint32_t)prop.multiProcessorCount;
@@ -707,6 +737,8 @@ static bool use_bucket_ctx(const divans_gpu_codec* c, bool has_segs) {
 static bool use_bucket_mix_bt(const divans_gpu_codec* c, bool has_segs) {
     return c->bucket_mix_bt_ok && (c->encode_path == 2u || (c->encode_path == 0u && !has_segs));
 }
+// The strides 2, 3, 4 and 8 (bucket_stride > 1) included: "automatic" takes the bucketed pass for their calls without a segment list by the
+// rule of the other passes -- ahead of the streaming kernels at 16 384 and at 64 streams (16 against 95 ms, 5 against 50 ms: DESIGN.md section 7, round 12)
 static bool use_bucket(const divans_gpu_codec* c) { return c->bucket_ok && c->encode_path != 1u && !c->geom.wrap_check; }   // task ids are stream * 256 + byte in 32 bits: callers keep n_streams < 2^24
 
 // The bucketed passes' work arrays are one allocation (c->d_bk) that only grows; each pass carves it in its own order.
@@ -784,7 +816,7 @@ extern "C" int divans_gpu_codec_set_block_types(divans_gpu_codec* c, uint32_t n_
     const uint32_t slots = derive_high_row_slots(g, blob);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    c->geom = g; c->high_row_slots = slots;
+    c->geom = g; c->high_row_slots = slots; c->stride_dist = derive_stride_distance(c->cfg, g, blob);
     free_tables(c);
     // the block types change the LDS the context tables take, not what the caller chose before: keep an explicitly set
     // grid / cache organisation / decoder generation, clamped to what still fits the LDS (and to caches the new row count allows)
@@ -811,7 +843,8 @@ extern "C" int divans_gpu_codec_set_encode_path(divans_gpu_codec* c, uint32_t pa
     if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
     if (path > 2u) return fail(DIVANS_GPU_EINVAL, "path must be 0 (automatic), 1 (streaming) or 2 (bucketed)");
     if (path == 2u && !c->bucket_ok && !c->bucket_mix_ok && !c->bucket_ctx_ok && !c->bucket_ctx_mix_ok && !c->bucket_mix_bt_ok)
-        return fail(DIVANS_GPU_EINVAL, "the bucketed encoder needs streams of at most 65536 bytes and either mixing value 4 everywhere (with no context map and no mixing, or "
+        return fail(DIVANS_GPU_EINVAL, "the bucketed encoder needs streams of at most 65536 bytes and either one stride distance of 2, 3, 4 or 8 everywhere (mixing values 5, 6, 7, "
+                                       "or 8 and above) with a constant context, no mixing and speeds whose row totals stay inside i16, or mixing value 4 everywhere (with no context map and no mixing, or "
                                        "with dynamic mixing and one literal block type, or with dynamic mixing and several block types provided that no "
                                        "previous byte reaches more than eight contexts: divans_gpu_codec_high_row_slots) or mixing value 0 everywhere with a context map that is not constant "
                                        "(any mixing, up to 8 literal block types, speeds whose row totals stay inside i16)");
@@ -828,6 +861,12 @@ extern "C" int divans_gpu_codec_last_encode_path(divans_gpu_codec* c, uint32_t* 
 extern "C" int divans_gpu_codec_high_row_slots(divans_gpu_codec* c, uint32_t* slots) {
     if (!c || !slots) return fail(DIVANS_GPU_EINVAL, "null argument");
     *slots = c->high_row_slots;
+    return 0;
+}
+
+extern "C" int divans_gpu_codec_bucket_stride(divans_gpu_codec* c, uint32_t* distance) {
+    if (!c || !distance) return fail(DIVANS_GPU_EINVAL, "null argument");
+    *distance = c->bucket_stride;
     return 0;
 }
 
@@ -1133,7 +1172,11 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
         view.sf = k.sf; view.stride = k.sf_stride;
         view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 3u;
         return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
-                                  [&](const BucketBatch& kk) -> int { HIP_TRY(launch_bucket_model(kk, c->num_cus * 4u, c->stream)); return 0; }, after);
+                                  [&](const BucketBatch& kk) -> int {
+                                      if (c->bucket_stride > 1u) HIP_TRY(launch_bucket_stride_model(kk, c->bucket_stride, c->num_cus * 4u, c->stream));
+                                      else HIP_TRY(launch_bucket_model(kk, c->num_cus * 4u, c->stream));
+                                      return 0;
+                                  }, after);
     }
     if (use_bucket_mix(c) && segs_ok) {
         MixBucketBatch k;

@@ -11,6 +11,9 @@
 //                            (1 high + 16 low) in LDS -- no table in HBM, no row cache, no cross-lane traffic (the loop
 //                            is explained at bk_chain_loop, lit_bucket_dev.h, which the two-model pass runs),
 //   4. bucket_unsort_kernel  puts the (start,freq) pairs back into position order for the rANS pass.
+// The strides 2, 3, 4 and 8 (every reachable mixing value 5, 6, 7, or 8 and above; constant context) run the same pass: there the
+// high row is [ctx][b_d] and the low row [b_d][hi] with b_d the byte d places back (literal.rs:192-208), so only step 1 differs --
+// bucket_sort_stride_kernel keys a position by that byte (launch_bucket_stride_model); steps 2-4 never look at what the key was.
 // The arithmetic per nibble is the same as everywhere else (probability/interface.rs:97-108, frequentist_cdf.rs:74-85).
 // The decoder cannot do this (it learns the bytes one at a time) and keeps the streaming kernels.
 #include "lit_bucket_dev.h"
@@ -347,6 +350,55 @@ __global__ __launch_bounds__(1024) void bucket_unsort32_kernel(const BucketBatch
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// 1'. the sort for a stride distance D = dist in {2, 3, 4, 8} (mixing values 5, 6, 7 and 8 and above under a constant context: high
+//     row [ctx][b_D], low row [b_D][hi] with b_D the byte D places back, literal.rs:184-208): the key of position p is in[p - D], and 0
+//     for p < D (a fresh stream's last_8_literals is zero; nothing in front of the stream is read).  A piece needs the D bytes in
+//     front of its base: piece_in[16 - D .. 16).
+//     SEG: position j < min(D, len) of a segment takes its key from the segment's last8 at distance D - j -- the byte lane
+//     bucket_sort_kernel<true> reads distance 1 from; a segment shorter than D hands nothing on (the next one brings its own last8),
+//     and a segment that starts up to D - 1 positions before the piece base still patches the keys that fall into this piece.
+//     Ranking, scan and placement are bk_sort_piece (lit_bucket_dev.h); tasks, chains and unsort never look at what the key was.
+// ---------------------------------------------------------------------------------------------
+template <bool SEG>
+__global__ __launch_bounds__(BK_SORT_THREADS) void bucket_sort_stride_kernel(const BucketBatch b, const uint32_t dist) {
+    __shared__ __attribute__((aligned(16))) unsigned long long staging64[BK_PIECE / 8u];
+    __shared__ __attribute__((aligned(16))) uint8_t piece_in[16 + BK_PIECE];
+    __shared__ uint32_t hist[4][256];
+    __shared__ uint32_t wsum[4];
+    __shared__ uint8_t key_lds[SEG ? BK_PIECE : 1u];     // SEG: the key of every position
+    const uint32_t s = blockIdx.x / b.pieces, piece = blockIdx.x % b.pieces;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t len = b.in_sizes ? b.in_sizes[s] : b.stream_len;
+    const uint8_t* in = b.in + (b.in_offsets ? b.in_offsets[s] : (uint64_t)s * b.stream_len);
+    uint32_t* desc = b.desc + ((size_t)s * 256u + tid) * 8u + piece;
+    const uint32_t base = piece * BK_PIECE;
+    if (base >= len) {
+        *desc = 0u;
+        if (SEG && piece == 0u)     // an empty stream: its list still has to add up to it
+            bk_seg_walk(b.seg_begin, b.segs, s, 0u, ~0u, true, b.bt_first, b.n_btypes, b.status, wsum, [](uint32_t, uint32_t, uint64_t) {});
+        return;
+    }
+    const uint32_t n = len - base < BK_PIECE ? len - base : BK_PIECE;
+    for (uint32_t i = tid; i < 1024u; i += BK_SORT_THREADS) (&hist[0][0])[i] = 0u;
+    bk_load_piece(piece_in, in + base, n);
+    if (tid < dist) piece_in[16u - dist + tid] = base ? in[base - dist + tid] : 0u;     // base >= 8192 > dist, or the stream's start
+    __syncthreads();
+    const uint8_t* key_of = piece_in + 16u - dist;      // key_of[p] = the byte dist places before position p
+    if (SEG) {
+        for (uint32_t i = tid; i < n; i += BK_SORT_THREADS) key_lds[i] = key_of[i];
+        __syncthreads();
+        bk_seg_walk(b.seg_begin, b.segs, s, len, piece == 0u ? ~0u : base + n, piece == 0u, b.bt_first, b.n_btypes, b.status, wsum,
+                    [&](uint32_t q, uint32_t l, uint64_t l8) {
+                        const uint32_t own = l < dist ? l : dist;
+                        for (uint32_t j = 0; j < own; ++j)      // q + j - base wraps above n for a position in front of the piece
+                            if (q + j - base < n) key_lds[q + j - base] = (uint8_t)(l8 >> (64u - 8u * (dist - j)));
+                    });
+        __syncthreads();
+    }
+    bk_sort_piece(b, s, base, n, desc, SEG ? key_lds : key_of, piece_in + 16, staging64, hist, wsum);
+}
+
 uint32_t bucket_chain_lds_bytes() { return (64u * BK_LANE_DWORDS + 128u) * 4u; }
 
 // steps 2 and 4 on their own, for the two-model pass (lit_bucket_mix.hip) that brings its own sort and chain kernels
@@ -381,6 +433,23 @@ hipError_t launch_bucket_model(const BucketBatch& b, uint32_t chain_blocks, hipS
 #endif
     hipLaunchKernelGGL(bucket_chain_kernel, dim3(chain_blocks), dim3(64), bucket_chain_lds_bytes(), st, b);
     hipLaunchKernelGGL(bucket_unsort_kernel, dim3(b.n_streams * b.pieces), dim3(1024), 0, st, b);
+    return hipGetLastError();
+}
+
+// launch_bucket_model with the stride sort in place of bucket_sort_kernel (its instances behind every other kernel of the file)
+hipError_t launch_bucket_stride_model(const BucketBatch& b, uint32_t dist, uint32_t chain_blocks, hipStream_t st) {
+    if (!(dist == 2u || dist == 3u || dist == 4u || dist == 8u)) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(b.counters, 0, 64, st);
+    if (e != hipSuccess) return e;
+    if (b.pieces < 8u) {
+        e = hipMemsetAsync(b.desc, 0, (size_t)b.n_streams * 256u * 8u * sizeof(uint32_t), st);
+        if (e != hipSuccess) return e;
+    }
+    if (b.segs) hipLaunchKernelGGL(bucket_sort_stride_kernel<true>, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b, dist);
+    else hipLaunchKernelGGL(bucket_sort_stride_kernel<false>, dim3(b.n_streams * b.pieces), dim3(BK_SORT_THREADS), 0, st, b, dist);
+    launch_bucket_tasks(b, st);
+    launch_bucket_chain(b, chain_blocks, st);
+    launch_bucket_unsort(b, st);
     return hipGetLastError();
 }
 

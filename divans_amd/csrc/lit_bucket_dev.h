@@ -102,6 +102,73 @@ __device__ __forceinline__ void bk_seg_walk(const uint32_t* seg_begin, const Lit
     }
 }
 
+// What a sort kernel of lit_bucket.hip does once the keys of a piece are known: keys[p] (LDS) = the bucket key of position p of
+// the piece, bytes[p] (LDS) = its byte, n positions.  bucket_sort_stride_kernel runs it; bucket_sort_kernel holds the same
+// statements as its own text (on this function it compiles to other instructions, and the kernels of the default path keep theirs):
+// change the two together.  Leaves sorted / inv of the piece and *desc = first slot | count << 16 of key
+// threadIdx.x.  staging64 (BK_PIECE bytes), hist ([4][256], zeroed by the caller), wsum (4 words): LDS of the workgroup of
+// BK_SORT_THREADS lanes, all of which call this behind a barrier that has made keys, bytes and hist visible.
+__device__ __forceinline__ void bk_sort_piece(const BucketBatch& b, uint32_t s, uint32_t base, uint32_t n, uint32_t* desc, const uint8_t* keys,
+                                              const uint8_t* bytes, unsigned long long* staging64, uint32_t (*hist)[256], uint32_t* wsum) {
+    uint8_t* staging = (uint8_t*)staging64;
+    const uint32_t tid = threadIdx.x, w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63;
+    const size_t pl = b.slot;
+    // ONE ranking pass over the wave's 256 lane masks in LDS, as explained in bucket_sort_kernel
+    unsigned long long* mask_of = staging64 + w * 256u;     // relaxed atomics below: lanes meet in these words, nothing may be forwarded
+    const unsigned long long my_bit = 1ull << lane;
+    uint32_t kept[16];
+#pragma unroll
+    for (uint32_t bt = 0; bt < 32u; ++bt) {
+        uint32_t r = 0;
+        const uint32_t p = w * 2048u + bt * 64u + lane;
+        if (p < n) {
+            const uint32_t key = keys[p];
+            __hip_atomic_store(mask_of + key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_or(mask_of + key, my_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const unsigned long long same = __hip_atomic_load(mask_of + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const uint32_t rank = lanes_below(same), cnt = (uint32_t)__popcll(same);
+            const uint32_t before = hist[w][key];
+            r = before + rank;
+            if (rank == cnt - 1u) hist[w][key] = before + cnt;
+        }
+        if (bt & 1u) kept[bt >> 1] |= r << 16; else kept[bt >> 1] = r;
+    }
+    __syncthreads();
+    // the 256 totals' exclusive scan: each wave scans its 64 keys with shuffles, the four wave sums meet in LDS
+    const uint32_t c0 = hist[0][tid], c1 = hist[1][tid], c2 = hist[2][tid], c3 = hist[3][tid];
+    const uint32_t tot = c0 + c1 + c2 + c3;
+    uint32_t incl = tot;
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += v;
+    }
+    if (lane == 63u) wsum[w] = incl;
+    __syncthreads();
+    uint32_t start = incl - tot;
+    for (uint32_t j = 0; j < 3u; ++j) if (j < w) start += wsum[j];
+    hist[0][tid] = start; hist[1][tid] = start + c0; hist[2][tid] = start + c0 + c1; hist[3][tid] = start + c0 + c1 + c2;
+    *desc = start | (tot << 16);
+    __syncthreads();
+    // placement: the slot is the key's base for this wave + the kept rank
+    uint16_t* inv = b.inv + (size_t)s * pl + base;
+#pragma unroll
+    for (uint32_t bt = 0; bt < 32u; ++bt) {
+        const uint32_t p = w * 2048u + bt * 64u + lane;
+        if (p < n) {
+            const uint32_t key = keys[p], byte = bytes[p];
+            const uint32_t slot = hist[w][key] + ((kept[bt >> 1] >> (16u * (bt & 1u))) & 0xffffu);
+            staging[slot] = (uint8_t)byte;
+            inv[p] = (uint16_t)slot;
+        }
+    }
+    __syncthreads();
+    uint8_t* sorted = b.sorted + (size_t)s * pl + base;
+    for (uint32_t i = tid * 16u; i < n; i += BK_SORT_THREADS * 16u) {
+        if (i + 16u <= n) *(u32x4*)(sorted + i) = *(const u32x4*)(staging + i);
+        else for (uint32_t k = i; k < n; ++k) sorted[k] = staging[k];
+    }
+}
+
 // One nibble against a row of 8 dwords (16 x u16) in LDS, split into phases so that the two nibbles of a byte
 // (different rows) can be in flight together: read, pack (start | freq << 16), blend, write.
 struct BkRow { u32x4 w0, w1, a0, a1; int chi, cprev; };

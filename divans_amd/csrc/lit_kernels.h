@@ -97,7 +97,8 @@ struct RansBatch {
 };
 
 typedef unsigned int bk_u32x2 __attribute__((ext_vector_type(2)));
-// Bucketed encoder model pass (lit_bucket.hip): mixing value 4, no mixing, context constant or a function of the previous byte.
+// Bucketed encoder model pass (lit_bucket.hip): mixing value 4, no mixing, context constant or a function of the previous byte -- or
+// one stride distance of 2, 3, 4 or 8 under a constant context (launch_bucket_stride_model: the key is the byte that far back).
 // With a segment list only the sort kernel changes: a segment's last8 replaces the bytes before its first position in the bucket keys.
 struct BucketBatch {
     const uint8_t* in; const uint64_t* in_offsets; const uint32_t* in_sizes;
@@ -120,6 +121,9 @@ struct BucketBatch {
     uint32_t* status;           // device word: LIT_STATUS_BAD_SEGMENT
 };
 hipError_t launch_bucket_model(const BucketBatch& b, uint32_t chain_blocks, hipStream_t st);
+// The same pass keyed by the byte `dist` places back (2, 3, 4 or 8: mixing values 5, 6, 7, and 8 and above, under a constant context):
+// bucket_sort_stride_kernel in place of bucket_sort_kernel, every other kernel and every field of the batch as above
+hipError_t launch_bucket_stride_model(const BucketBatch& b, uint32_t dist, uint32_t chain_blocks, hipStream_t st);
 void launch_bucket_tasks(const BucketBatch& b, hipStream_t st);
 void launch_bucket_unsort(const BucketBatch& b, hipStream_t st);
 void launch_bucket_unsort32(const BucketBatch& b, hipStream_t st);   // the same for a plane of 4-byte elements

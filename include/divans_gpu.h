@@ -246,9 +246,16 @@ int divans_gpu_codec_set_geometry(divans_gpu_codec *c, uint32_t blocks, uint32_t
  * mixing values gets -- with a context map that is not constant, without mixing or with dynamic mixing, for any number of literal
  * block types (divans_gpu_codec_set_block_types), streams of at most 65536 bytes and speeds divans_gpu_speed_supported accepts.
  * There, too, it is what "automatic" picks for calls without a segment list.
+ * And it exists for the strides 2, 3, 4 and 8 with a constant context (lit_bucket.hip, bucket_sort_stride_kernel): every reachable
+ * mixing value at least 4 and all of one stride distance (5, 6, 7 -> 2, 3, 4; every value from 8 up -> 8, so a mask that mixes 8
+ * and 12 qualifies), no mixing, a constant context map, streams of at most 65536 bytes and speeds divans_gpu_speed_supported
+ * accepts.  The buckets are keyed by the byte that many places back (divans_gpu_codec_bucket_stride); "automatic" picks it for
+ * calls without a segment list.
  * Asking for path 2 elsewhere is DIVANS_GPU_EINVAL: mixing value 0 with a constant context (one bucket per stream), mixing value 4
  * with UTF8 / SIGN and no mixing, or with mixing and several block types of which some previous byte reaches more than eight contexts
- * (divans_gpu_codec_high_row_slots), strides, table-driven masks, longer streams.
+ * (divans_gpu_codec_high_row_slots), strides with two models or under a context that is not constant (the high row would need two
+ * key bytes, the previous one and the one at the stride distance), masks that mix stride distances or hold a value below 4 next to
+ * one above (table-driven masks), longer streams.
  * A call WITH a segment list (divans_gpu_lit_encode_segments_batch) takes the bucketed pass only under path 2 -- a segment's last8
  * then replaces the bytes before its first position in the bucket keys -- and the streaming kernels under "automatic". */
 int divans_gpu_codec_set_encode_path(divans_gpu_codec *c, uint32_t path);
@@ -261,6 +268,10 @@ int divans_gpu_codec_last_encode_path(divans_gpu_codec *c, uint32_t *path);
  * path 2 exists where this number is at most 8 -- brotli's clustered context maps stay far below it -- and the codec's context map is
  * not constant; there, too, it is what "automatic" picks for calls without a segment list, and a list takes it under path 2.  For a codec with one block type the number says how many of the eight rows its buckets use. */
 int divans_gpu_codec_high_row_slots(divans_gpu_codec *c, uint32_t *slots);
+/* The distance the bucketed ONE-model pass (lit_bucket.hip) keys its buckets by: 1 where every mixing value is 4 (the byte before),
+ * 2, 3, 4 or 8 where every reachable mixing value selects that stride and the context is constant, 0 where the codec has no such
+ * pass (two models, context-keyed rows, mixed distances, a stride under a context map, streams above 65536 bytes). */
+int divans_gpu_codec_bucket_stride(divans_gpu_codec *c, uint32_t *distance);
 /* Streams the bucketed two-model pass takes per launch sequence (default 32768, halved until its work arrays -- 1.9 MB
  * per 64 KiB stream -- fit the device).  A tuning / test knob: the coded bytes do not depend on it. */
 int divans_gpu_codec_set_bucket_batch(divans_gpu_codec *c, uint32_t streams);
