@@ -198,6 +198,31 @@ void orc_lit_state_free(orc_lit_state *s) {
     free(s);
 }
 
+/* A new state writes 12 MB of default rows; lit_state_reset re-arms only the rows a stream touched (the batch workers below code
+ * stream after stream on one state that way).  The one-call entry points keep up to SPARE_STATES states between calls, so that a
+ * test that codes thousands of short streams does not pay for the tables every time.  Any thread may take and give back. */
+#define SPARE_STATES 8
+static pthread_mutex_t spare_lock = PTHREAD_MUTEX_INITIALIZER;
+static orc_lit_state *spare_states[SPARE_STATES];
+static int n_spare_states;
+
+static orc_lit_state *state_take(const orc_lit_config *cfg) {
+    orc_lit_state *s = NULL;
+    pthread_mutex_lock(&spare_lock);
+    if (n_spare_states > 0) s = spare_states[--n_spare_states];
+    pthread_mutex_unlock(&spare_lock);
+    if (!s) return orc_lit_state_new(cfg);
+    lit_state_reset(s, cfg);
+    return s;
+}
+
+static void state_give_back(orc_lit_state *s) {
+    pthread_mutex_lock(&spare_lock);
+    if (n_spare_states < SPARE_STATES) { spare_states[n_spare_states++] = s; s = NULL; }
+    pthread_mutex_unlock(&spare_lock);
+    orc_lit_state_free(s);
+}
+
 void orc_lit_set_last8(orc_lit_state *s, uint64_t last8) { s->last_8_literals = last8; }
 uint64_t orc_lit_get_last8(const orc_lit_state *s) { return s->last_8_literals; }
 
@@ -331,24 +356,24 @@ static int stream_decode_with(orc_lit_state *s, const orc_lit_config *cfg, const
 }
 
 size_t orc_lit_stream_encode(const orc_lit_config *cfg, const uint8_t *in, size_t n, uint8_t *out, size_t cap) {
-    orc_lit_state *s = orc_lit_state_new(cfg);
+    orc_lit_state *s = state_take(cfg);
     size_t r = stream_encode_with(s, cfg, in, n, out, cap, NULL);
-    orc_lit_state_free(s);
+    state_give_back(s);
     return r;
 }
 
 size_t orc_lit_stream_encode_trace(const orc_lit_config *cfg, const uint8_t *in, size_t n,
                                    uint8_t *out, size_t cap, int16_t *trace) {
-    orc_lit_state *s = orc_lit_state_new(cfg);
+    orc_lit_state *s = state_take(cfg);
     size_t r = stream_encode_with(s, cfg, in, n, out, cap, trace);
-    orc_lit_state_free(s);
+    state_give_back(s);
     return r;
 }
 
 int orc_lit_stream_decode(const orc_lit_config *cfg, const uint8_t *in, size_t in_len, uint8_t *out, size_t n) {
-    orc_lit_state *s = orc_lit_state_new(cfg);
+    orc_lit_state *s = state_take(cfg);
     int r = stream_decode_with(s, cfg, in, in_len, out, n);
-    orc_lit_state_free(s);
+    state_give_back(s);
     return r;
 }
 
@@ -562,7 +587,7 @@ size_t orc_lit_segments_encode(const orc_lit_config *cfg, const uint8_t *lit, si
                                const uint32_t *seg_btype, const uint64_t *seg_last8, size_t nseg, uint8_t *out, size_t cap) {
     orc_lit_config *c = (orc_lit_config *)malloc(sizeof(*c));
     memcpy(c, cfg, sizeof(*c));
-    orc_lit_state *s = orc_lit_state_new(c);
+    orc_lit_state *s = state_take(c);
     orc_ans_encoder enc;
     orc_ans_encoder_init(&enc);
     size_t pos = 0;
@@ -577,7 +602,7 @@ size_t orc_lit_segments_encode(const orc_lit_config *cfg, const uint8_t *lit, si
     if (enc.failed || ret > cap || pos != n) ret = (size_t)-1;
     else memcpy(out, enc.out.data, ret);
     orc_ans_encoder_free(&enc);
-    orc_lit_state_free(s); free(c);
+    state_give_back(s); free(c);
     return ret;
 }
 
@@ -585,7 +610,7 @@ int orc_lit_segments_decode(const orc_lit_config *cfg, const uint8_t *in, size_t
                             const uint32_t *seg_btype, const uint64_t *seg_last8, size_t nseg, uint8_t *out, size_t n) {
     orc_lit_config *c = (orc_lit_config *)malloc(sizeof(*c));
     memcpy(c, cfg, sizeof(*c));
-    orc_lit_state *s = orc_lit_state_new(c);
+    orc_lit_state *s = state_take(c);
     orc_ans_decoder dec;
     orc_ans_decoder_init(&dec, in, in_len);
     size_t pos = 0;
@@ -596,6 +621,6 @@ int orc_lit_segments_decode(const orc_lit_config *cfg, const uint8_t *in, size_t
         pos += seg_len[k];
     }
     int rc = (dec.starved || pos != n) ? -1 : 0;
-    orc_lit_state_free(s); free(c);
+    state_give_back(s); free(c);
     return rc;
 }

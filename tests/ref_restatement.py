@@ -235,8 +235,8 @@ class LiteralCoder:
     """LiteralState::code_nibble_array + code_nibble with the LiteralBookKeeping fields they read."""
 
     def __init__(self, context_map, mixing_mask, prediction_mode, btype, mixing_param, speeds):
-        self.cmap = [int(x) for x in context_map]
-        self.mixing_mask = [int(x) for x in mixing_mask]
+        self.cmap = list(bytes(context_map))                 # (bytes or small ints in, ints out: a coder per short stream must be cheap)
+        self.mixing_mask = list(bytes(mixing_mask))
         self.lut0, self.lut1 = context_luts(prediction_mode)
         self.btype = btype
         self.speeds = [(int(a), int(b)) for a, b in speeds]
