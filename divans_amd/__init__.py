@@ -187,6 +187,7 @@ def load_library():
     L.divans_gpu_selftest_cdf_ops.argtypes = [vp, vp, u32, vp]
     L.divans_gpu_selftest_cdf_ops_on.argtypes = [vp, u32, vp, u32, vp]
     L.divans_gpu_selftest_rans_pairs.argtypes = [vp, vp, u32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.divans_gpu_selftest_rans_batch.argtypes = [vp, u32, vp, u32, vp, u32, u64, ctypes.c_uint8, u32, vp, vp, vp, u32, vp, ctypes.c_size_t, ctypes.POINTER(u32)]
     L.divans_gpu_codec_set_block_types.argtypes = [vp, u32]
     L.divans_gpu_lit_encode_segments_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, u64, vp, vp]
     L.divans_gpu_lit_decode_segments_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32]
@@ -234,7 +235,7 @@ def exported_symbols():
         "divans_gpu_codec_set_geometry", "divans_gpu_codec_set_split_cache", "divans_gpu_codec_tune_tables", "divans_gpu_codec_search_tables", "divans_gpu_codec_table_placement", "divans_gpu_table_memory", "divans_gpu_set_table_va_cap", "divans_gpu_trim", "divans_gpu_codec_set_decoder", "divans_gpu_experimental_decoders", "divans_gpu_codec_set_byte_order", "divans_gpu_codec_byte_order", "divans_gpu_codec_row_replay", "divans_gpu_codec_set_rans_split", "divans_gpu_codec_set_encode_path", "divans_gpu_codec_last_encode_path", "divans_gpu_codec_set_bucket_batch", "divans_gpu_codec_high_row_slots", "divans_gpu_codec_bucket_stride", "divans_gpu_lit_model_batch",
         "divans_gpu_selftest_division", "divans_gpu_speed_supported", "divans_gpu_speed_accepted", "divans_gpu_codec_status", "divans_gpu_codec_clear_status", "divans_gpu_codec_status_async", "divans_gpu_codec_last_decode_kernel", "divans_gpu_codec_set_stream_flags", "divans_gpu_codec_set_block_types",
         "divans_gpu_lit_encode_segments_batch", "divans_gpu_lit_decode_segments_batch",
-        "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_cdf_ops_on", "divans_gpu_selftest_rans_pairs", "divans_gpu_lit_encode_batch_chunks",
+        "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_cdf_ops_on", "divans_gpu_selftest_rans_pairs", "divans_gpu_selftest_rans_batch", "divans_gpu_lit_encode_batch_chunks",
         "divans_gpu_lit_encode_host_pipelined", "divans_gpu_lit_decode_host_pipelined", "divans_gpu_host_alloc", "divans_gpu_host_free",
         "divans_gpu_lit_stream_begin", "divans_gpu_lit_stream_encode", "divans_gpu_lit_stream_finish",
         "divans_gpu_lit_stream_decode_begin", "divans_gpu_lit_stream_decode",
@@ -519,6 +520,27 @@ class LiteralCodec:
         _check(self._lib.divans_gpu_selftest_rans_pairs(self._h, pairs.ctypes.data, pairs.size, out.ctypes.data, cap, ctypes.byref(n)),
                "divans_gpu_selftest_rans_pairs")
         return out[:n.value].copy()
+
+    def selftest_rans_batch(self, impl, pairs, sizes, out_base=0, fill=0xA5, guard=256):
+        """divans_gpu_selftest_rans_batch: pairs (n, sf_stride) uint32 rows of start | freq << 16, sizes = bytes per stream; impl 0 one lane
+        per stream, 1 one lane per chunk, 2 two lanes per chunk.  Returns dict(offsets, sizes, chunk_bytes (n, max_chunks), area = guard +
+        n slots + guard as the launch left it, slot, guard, status)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
+        sizes = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+        n = sizes.size
+        assert pairs.ndim == 2 and pairs.shape[0] == n
+        longest = int(sizes.max()) if n else 0
+        slot = encode_bound(longest)
+        max_chunks = max(1, (2 * longest + 65535) >> 16)
+        offs = np.zeros(n, dtype=np.uint64); out_sizes = np.zeros(n, dtype=np.uint32)
+        chunk_bytes = np.zeros((n, max_chunks), dtype=np.uint32)
+        area = np.empty(2 * guard + n * slot, dtype=np.uint8)
+        status = ctypes.c_uint32(0)
+        _check(self._lib.divans_gpu_selftest_rans_batch(self._h, int(impl), pairs.ctypes.data, pairs.shape[1], sizes.ctypes.data, n, int(out_base),
+                                                        int(fill), int(guard), offs.ctypes.data, out_sizes.ctypes.data, chunk_bytes.ctypes.data,
+                                                        max_chunks, area.ctypes.data, area.size, ctypes.byref(status)),
+               "divans_gpu_selftest_rans_batch")
+        return dict(offsets=offs, sizes=out_sizes, chunk_bytes=chunk_bytes, area=area, slot=slot, guard=guard, status=int(status.value))
 
     def selftest_division(self):
         m = ctypes.c_uint64(0)

@@ -1835,6 +1835,65 @@ extern "C" int divans_gpu_selftest_rans_pairs(divans_gpu_codec* c, const uint32_
     return 0;
 }
 
+// The rANS pass alone on a BATCH of caller-supplied pair rows, through launch_rans_encode as the encode entry points call it
+// (include/divans_gpu.h): impl 0 = rans_encode_kernel, 1 = rans_encode2_kernel + rans_stitch_kernel, 2 = rans_encode2_split_kernel +
+// rans_stitch_kernel.  The output area -- guard, n_streams slots, guard -- is filled with `fill` first and comes back whole.
+extern "C" int divans_gpu_selftest_rans_batch(divans_gpu_codec* c, uint32_t impl, const uint32_t* pairs, uint32_t sf_stride, const uint32_t* sizes,
+                                              uint32_t n_streams, uint64_t out_base, uint8_t fill, uint32_t guard_bytes, uint64_t* out_offsets,
+                                              uint32_t* out_sizes, uint32_t* chunk_bytes, uint32_t max_chunks, uint8_t* area, size_t area_cap,
+                                              uint32_t* status_out) {
+    if (!c || !sizes || !out_offsets || !out_sizes || !chunk_bytes || !area || n_streams == 0) return fail(DIVANS_GPU_EINVAL, "null argument or empty batch");
+    if (impl > 2u) return fail(DIVANS_GPU_EINVAL, "impl is 0 (one lane per stream), 1 (one lane per chunk) or 2 (two lanes per chunk)");
+    if (guard_bytes < 256u || guard_bytes % 16u) return fail(DIVANS_GPU_EINVAL, "the guard zones are a multiple of 16 and at least 256 bytes");
+    uint32_t longest = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) longest = std::max(longest, sizes[i]);
+    if (impl != 0u && longest > 65536u) return fail(DIVANS_GPU_EINVAL, "the chunk-parallel kernels take streams of at most 65 536 bytes");
+    if (sf_stride % 4u || 2ull * longest > sf_stride) return fail(DIVANS_GPU_EINVAL, "sf_stride is a multiple of 4 and at least twice the longest stream");
+    if (sf_stride && !pairs) return fail(DIVANS_GPU_EINVAL, "null argument or empty batch");
+    const uint32_t need_chunks = std::max<uint32_t>(1u, (uint32_t)((2ull * longest + 65535ull) >> 16));
+    if (max_chunks < need_chunks) return fail(DIVANS_GPU_EINVAL, "max_chunks too small");
+    const uint64_t slot = divans_gpu_lit_encode_bound(longest);
+    const size_t area_bytes = 2u * (size_t)guard_bytes + (size_t)n_streams * slot;
+    if (area_cap < area_bytes) return fail(DIVANS_GPU_ECAP, "output area too small: 2 * guard_bytes + n_streams * divans_gpu_lit_encode_bound(longest)");
+    HIP_TRY(hipSetDevice(c->device));
+    RansBatch r;
+    std::memset(&r, 0, sizeof(r));
+    if (impl != 0u) { int rr = ensure_rans_scratch(c, n_streams, SfView(), r); if (rr) return rr; }
+    const size_t sf_bytes = (size_t)n_streams * sf_stride * 4u, cb_bytes = (size_t)n_streams * max_chunks * 4u;
+    uint32_t* d_sf = nullptr; uint8_t* d_area = nullptr; uint64_t* d_off = nullptr; uint32_t* d_sz = nullptr; uint32_t* d_len = nullptr; uint32_t* d_cb = nullptr;
+    hipError_t e = hipMalloc(&d_sf, sf_bytes + 64u);
+    if (e == hipSuccess) e = hipMalloc(&d_area, area_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_off, (size_t)n_streams * 8u);
+    if (e == hipSuccess) e = hipMalloc(&d_sz, (size_t)n_streams * 4u);
+    if (e == hipSuccess) e = hipMalloc(&d_len, (size_t)n_streams * 4u);
+    if (e == hipSuccess) e = hipMalloc(&d_cb, cb_bytes);
+    uint32_t status = 0;
+    if (e == hipSuccess && sf_bytes) e = hipMemcpyAsync(d_sf, pairs, sf_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_len, sizes, (size_t)n_streams * 4u, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_area, fill, area_bytes, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cb, 0, cb_bytes, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_status, 0, 4, c->stream);
+    if (e == hipSuccess) {
+        r.sf = d_sf; r.n_streams = n_streams; r.stream_len = longest; r.max_stream_len = longest; r.sf_stride = sf_stride; r.in_sizes = d_len;
+        r.out_base = out_base; r.out = d_area + guard_bytes; r.out_slot = slot; r.out_offsets = d_off; r.out_sizes = d_sz; r.status = c->d_status;
+        r.chunk_bytes = d_cb; r.max_chunks = max_chunks;
+        r.split_states = impl == 2u ? 1u : 0u;       // (scratch stays null for impl 0: the one-lane-per-stream kernel, any number of chunks)
+        e = launch_rans_encode(r, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_offsets, d_off, (size_t)n_streams * 8u, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_sizes, d_sz, (size_t)n_streams * 4u, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(chunk_bytes, d_cb, cb_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(area, d_area, area_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&status, c->d_status, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_status, 0, 4, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_sf); (void)hipFree(d_area); (void)hipFree(d_off); (void)hipFree(d_sz); (void)hipFree(d_len); (void)hipFree(d_cb);
+    if (e != hipSuccess) return fail(DIVANS_GPU_EHIP, hipGetErrorString(e));
+    if (status_out) *status_out = status;
+    if (status & LIT_STATUS_BAD_MODEL) return fail(DIVANS_GPU_EINVAL, "invalid (start,freq) pair");
+    return 0;
+}
+
 // ---- host-memory convenience wrappers ----------------------------------------------------------
 extern "C" int divans_gpu_lit_encode_host(divans_gpu_codec* c, const uint8_t* in, uint32_t stream_len, uint32_t n_streams,
                                           uint8_t* out_packed, size_t out_cap, uint64_t* out_offsets, uint32_t* out_sizes,

@@ -395,7 +395,25 @@ int divans_gpu_speed_accepted(int32_t inc, int32_t lim);
  * cdf_ops_on runs the script on one of the device's restatements of that arithmetic: impl 0 = the generation-1 streaming kernels
  *   (what cdf_ops runs), 1 = lit_decode2.hip, 2 = the bucketed encoder passes (packed rows of lit_bucket_dev.h + mix_nibble; it has
  *   no decoder: EINVAL for op 9), 3 = lit_decode_t.hip (experiment builds; EINVAL otherwise).  Same script, same records.
- * rans_pairs: the LIFO rANS pass on n_pairs (even) caller-supplied (start | freq << 16) words of one stream. */
+ * rans_pairs: the LIFO rANS pass on n_pairs (even) caller-supplied (start | freq << 16) words of one stream.
+ * rans_batch: the rANS pass of the encode entry points on a batch of caller-supplied pair rows, host memory in and out, through the
+ *   launcher those entry points use: impl 0 = one lane per stream (any number of 65 536-symbol chunks), 1 = one lane per chunk plus
+ *   the stitch, 2 = two lanes per chunk (one per rANS state) plus the stitch; 1 and 2 take streams of at most 65 536 bytes (EINVAL
+ *   above that) and code chunk 0 into the codec's chunk scratch, sized as the encode calls size it.
+ *   pairs = [n_streams][sf_stride] words start | freq << 16, oldest first; sf_stride a multiple of 4 and >= 2 * the longest size
+ *   (what lies behind a stream's 2 * size pairs is never coded).  sizes[i] = BYTES of stream i (2 * sizes[i] symbols), always handed
+ *   to the kernels as per-stream sizes.  The output area is guard_bytes (a multiple of 16, >= 256), then n_streams slots of
+ *   divans_gpu_lit_encode_bound(longest size), then guard_bytes again; the whole area is set to `fill` before the launch and copied
+ *   to `area` (area_cap >= its size, else ECAP) afterwards, so the caller sees every byte the launch left alone.
+ *   out_offsets[i] = out_base + where stream i begins, counted from the first slot (area index guard_bytes + out_offsets[i] -
+ *   out_base); a stream ends at its slot's end; an empty stream reports size 0 at the slot's end.  chunk_bytes[i * max_chunks + k]
+ *   = coded bytes of chunk k (0 where the stream has no such chunk); max_chunks >= the chunks of the longest stream.
+ *   A pair with freq == 0, freq >= 32768 or start >= 32768 raises DIVANS_GPU_STATUS_BAD_MODEL, which comes back as EINVAL.
+ *   *status_out (may be NULL) receives the device status word of the launch; the word is cleared before the call returns. */
+int divans_gpu_selftest_rans_batch(divans_gpu_codec *c, uint32_t impl, const uint32_t *pairs, uint32_t sf_stride, const uint32_t *sizes,
+                                   uint32_t n_streams, uint64_t out_base, uint8_t fill, uint32_t guard_bytes, uint64_t *out_offsets,
+                                   uint32_t *out_sizes, uint32_t *chunk_bytes, uint32_t max_chunks, uint8_t *area, size_t area_cap,
+                                   uint32_t *status_out);
 int divans_gpu_selftest_cdf_ops(divans_gpu_codec *c, const uint32_t *ops, uint32_t n_ops, int32_t *out);
 int divans_gpu_selftest_cdf_ops_on(divans_gpu_codec *c, uint32_t impl, const uint32_t *ops, uint32_t n_ops, int32_t *out);
 int divans_gpu_selftest_rans_pairs(divans_gpu_codec *c, const uint32_t *pairs, uint32_t n_pairs, uint8_t *out, size_t cap, size_t *out_len);

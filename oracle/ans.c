@@ -88,6 +88,31 @@ void orc_ans_put_start_freq(orc_ans_encoder *e, orc_prob start, orc_prob freq) {
     if (e->n_pending == ORC_ANS_NUM_SYMBOLS_BEFORE_FLUSH) orc_ans_flush_chunk(e);
 }
 
+/* The encoder on caller-supplied pairs (start | freq << 16, oldest first): put_start_freq for each, one final flush_chunk.
+ * out receives the coded bytes in the order the decoder reads them, chunk_bytes[k] the bytes of the k-th 65 536-symbol chunk.
+ * Returns the coded size, or (size_t)-1 when out / chunk_bytes are too small or a pair tripped the reference's debug_asserts. */
+size_t orc_ans_encode_pairs(const uint32_t *pairs, size_t n_pairs, uint8_t *out, size_t out_cap, uint32_t *chunk_bytes, size_t max_chunks,
+                            size_t *n_chunks) {
+    orc_ans_encoder e;
+    orc_ans_encoder_init(&e);
+    size_t chunks = 0, done = 0;
+    int short_of_room = 0;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        orc_ans_put_start_freq(&e, (orc_prob)(pairs[i] & 0xffffu), (orc_prob)(pairs[i] >> 16));
+        if (i + 1 == n_pairs) orc_ans_flush_chunk(&e);
+        if (e.out.len != done) {        /* a chunk left: full inside put_start_freq, or the last one just above */
+            if (chunks < max_chunks) chunk_bytes[chunks] = (uint32_t)(e.out.len - done); else short_of_room = 1;
+            ++chunks; done = e.out.len;
+        }
+    }
+    size_t r = e.out.len;
+    if (e.failed || short_of_room || r > out_cap) r = (size_t)-1;
+    else if (r) memcpy(out, e.out.data, r);
+    if (n_chunks) *n_chunks = chunks;
+    orc_ans_encoder_free(&e);
+    return r;
+}
+
 /* ans.rs:279-286 */
 void orc_ans_put_nibble(orc_ans_encoder *e, uint8_t sym, const orc_cdf16 *cdf, orc_sym_start_freq *coded) {
     orc_sym_start_freq sf;

@@ -95,6 +95,9 @@ void orc_ans_encoder_free(orc_ans_encoder *e);
 void orc_ans_put_start_freq(orc_ans_encoder *e, orc_prob start, orc_prob freq); /* ans.rs:287-301 */
 void orc_ans_put_nibble(orc_ans_encoder *e, uint8_t sym, const orc_cdf16 *cdf, orc_sym_start_freq *coded); /* ans.rs:279-286 */
 void orc_ans_flush_chunk(orc_ans_encoder *e);                                   /* ans.rs:331-378 */
+/* put_start_freq over pairs[i] = start | freq << 16 (oldest first) + the final flush_chunk: coded bytes and the size of every chunk */
+size_t orc_ans_encode_pairs(const uint32_t *pairs, size_t n_pairs, uint8_t *out, size_t out_cap, uint32_t *chunk_bytes, size_t max_chunks,
+                            size_t *n_chunks);
 
 typedef struct {
     uint64_t state_a, state_b; /* ans.rs:142-162 */

@@ -126,6 +126,9 @@ def lib(native=False):
     L.orc_lit_batch_check.restype = ctypes.c_long
     L.orc_lit_batch_check.argtypes = [ctypes.POINTER(LitConfig), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    L.orc_ans_encode_pairs.restype = ctypes.c_size_t
+    L.orc_ans_encode_pairs.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.POINTER(ctypes.c_size_t)]
     L.orc_cdf_default.argtypes = [ctypes.POINTER(Cdf16)]
     L.orc_cdf_blend.argtypes = [ctypes.POINTER(Cdf16), ctypes.c_uint8, Speed]
     L.orc_cdf_average.argtypes = [ctypes.POINTER(Cdf16), ctypes.POINTER(Cdf16), ctypes.c_int32, ctypes.POINTER(Cdf16)]
@@ -195,6 +198,18 @@ def lit_encode(cfg, data, trace=False):
         raise RuntimeError("oracle encode failed")
     coded = out[:r].copy()
     return (coded, tr) if trace else coded
+
+
+def ans_encode_pairs(pairs):
+    """ANSEncoder on (start | freq << 16) words, oldest first (orc_ans_encode_pairs): (coded bytes, list of per-chunk sizes)."""
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1)
+    max_chunks = (pairs.size + 65535) // 65536 + 1
+    cap = 16 * max_chunks + 4 * pairs.size
+    out = np.empty(max(cap, 1), dtype=np.uint8); cb = np.zeros(max_chunks, dtype=np.uint32); n = ctypes.c_size_t(0)
+    r = lib().orc_ans_encode_pairs(pairs.ctypes.data, pairs.size, out.ctypes.data, cap, cb.ctypes.data, max_chunks, ctypes.byref(n))
+    if r == ctypes.c_size_t(-1).value:
+        raise RuntimeError("oracle rANS encode failed (a pair outside the reference's domain)")
+    return out[:r].copy(), [int(x) for x in cb[:n.value]]
 
 
 def lit_batch_check(cfg, blocks, coded, offsets, sizes, threads=1):
