@@ -131,6 +131,10 @@ struct divans_gpu_codec {
 #endif
     bool dm_auto = DIVANS_DM_AUTO_DEFAULT != 0;          // nobody chose between direct-mapped and 2-way caches (divans_gpu_codec_set_decoder): pick per batch
     uint32_t dm_log2 = 0, dm_shift = 0;   // LitBatch::dm_log2 / dm_shift
+#ifndef DIVANS_D2_PIN_DEFAULT     // experiment switch: 0 = the high stride rows are pinned only on request
+#define DIVANS_D2_PIN_DEFAULT 1
+#endif
+    uint32_t hs_pin = DIVANS_D2_PIN_DEFAULT ? 0u : 1u;   // divans_gpu_codec_set_high_row_pinning: 0 by the byte order, 1 never, 2 wherever an instance exists
     uint32_t blocks2 = 0;                 // persistent grid of lit_decode2_kernel
     uint32_t blocks_t = 0, t_log2 = 0, t_shift = 0;   // generation 4 (lit_decode_t.hip, one lane per stream): grid of 64-stream workgroups, cache rows / shifts
     bool user_geometry = false;           // set_geometry / set_split_cache / set_decoder were called: set_block_types keeps their choices
@@ -961,6 +965,15 @@ static int set_decoder_impl(divans_gpu_codec* c, uint32_t generation, const uint
     return 0;
 }
 
+static int abort_search(divans_gpu_codec* c);
+extern "C" int divans_gpu_codec_set_high_row_pinning(divans_gpu_codec* c, uint32_t mode) {
+    if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
+    if (mode > 2u) return fail(DIVANS_GPU_EINVAL, "high-row pinning must be 0 (by the byte order), 1 (never: tagged caches) or 2 (wherever a pinned instance exists)");
+    if (mode != c->hs_pin) { const int rc = abort_search(c); if (rc) return rc; }     // placements are compared under one organisation
+    c->hs_pin = mode;
+    return 0;
+}
+
 extern "C" void divans_gpu_trim(void) { table_pool_drop(-1); }
 
 extern "C" int divans_gpu_codec_set_rans_split(divans_gpu_codec* c, uint32_t mode) {
@@ -1468,7 +1481,15 @@ static void decode2_shape(divans_gpu_codec* c, uint32_t n_streams, bool segs, Li
         }
         grid = std::min(grid, (n_streams + groups_per_block(c) - 1u) / groups_per_block(c));
     }
-    b.cache_bytes_per_wg = (LIT_THREADS / 16) * lit_decode2_stream_lds(b.dm_log2);
+    // The high stride rows of the plain stride-1 decoder: the rows of the most frequent previous bytes stay in LDS for the whole stream
+    // instead of competing for tagged sets (a rare byte then evicts nobody: 3.6-8.1 instead of 7.2-12.6 % of a text stream's high
+    // rows go to memory, tests/test_pinned_rows_cpu.py).  That presumes an order that ranks by frequency -- the learned one once it is
+    // there, or the caller's hint -- so numeric order, a first call before the order is learned and a caller who chose an organisation
+    // (divans_gpu_codec_set_decoder) keep the tagged caches.  b.byte_rank, b.geom and b.segs are set by now.
+    const bool by_order = c->hs_pin == 0u && c->dm_auto && b.byte_rank != nullptr;
+    const bool pinned = (c->hs_pin == 2u || by_order) && lit_decode2_can_pin(b, c->mix);
+    if (pinned) b.dm_shift = (b.dm_shift & 0x7fffffffu) | LIT_DM_PINNED;
+    b.cache_bytes_per_wg = (LIT_THREADS / 16) * lit_decode2_stream_lds(b.dm_log2, pinned);
 }
 
 static void placement_finish(divans_gpu_codec* c) {

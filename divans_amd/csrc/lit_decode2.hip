@@ -11,13 +11,16 @@
 //   * blend (probability/frequentist_cdf.rs:74-85): the renormalisation half sits behind a wave-level branch (with the
 //     reference's speeds a row renormalises once in hundreds of updates);
 //   * row caches: 2-way, both ways' data and the tag word are read in parallel (one LDS round trip), one cache per table so that
-//     the rows of one nibble never compete for a set;
+//     the rows of one nibble never compete for a set; the plain stride-1 decoder under a constant context instead PINS the high rows
+//     of the most frequent previous bytes in LDS (CM_PIN: no tags, a rare byte evicts nobody);
 //   * coded words: a 32-word ring per stream in LDS, topped up 16 words at a time (ans.rs:428-442 reads them in this order).
 //
 // Arithmetic and results are those of lit_decode_kernel (the parity tests run both against the oracle).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+
+#include <algorithm>
 
 #include "lit_device.h"
 
@@ -64,14 +67,19 @@ constexpr uint32_t kRingBytes = kRingWords * 4u;
 //    high half, so ONE ds_read_b32 per lane fetches both candidates while the set's tag word (way 0 row id | way 1 row id << 15 |
 //    most recently used way << 31) is read in parallel.
 // Either way a hit costs one LDS round trip.
+// The high stride rows of the plain stride-1 decoder under a constant context have a third organisation (CM_PIN): the row's low byte
+// is the rank of the previous byte in the launch's byte order, and the rows of ranks 0 .. P-1 LIVE in LDS slot `rank` for the whole
+// stream (filled with the default CDF at its start, never written to memory); every other high row is loaded and stored like an
+// uncached one.  No tags, no victims: a rare byte costs its own two requests and evicts nobody.
 struct DmCache {
     uint32_t data_off;   // LDS address of slot / set 0 of this stream's cache + (2 or 4) * lane-in-row
     uint32_t tag_off;    // LDS address of its tags
-    uint32_t mask;       // slots - 1 / sets - 1
+    uint32_t mask;       // slots - 1 / sets - 1; pinned: P, the number of slots
     uint32_t shift;      // index = (row ^ (row >> shift)) & mask
 };
 
 struct RowSlot { uint32_t row; uint32_t addr; bool missed; };   // missed: the row was requested with gload_async()
+constexpr uint32_t kNotInLds = 0u;      // RowSlot::addr of a row the pinned organisation keeps in memory (no cache starts at LDS address 0: the word ring does)
 
 struct Table2 {
     __amdgpu_buffer_rsrc_t rsrc;
@@ -95,11 +103,18 @@ struct Table2 {
     }
     // Every access of the coder is a read-modify-write of a whole row: a cached row is always dirty, a miss writes the
     // victim's row back (its data is in what the speculative read returned) and fetches the new one.
-    template <bool PRESENT, bool TWOWAY, bool ASYNC>
+    template <bool PRESENT, bool TWOWAY, bool ASYNC, bool PIN = false>
     __device__ __forceinline__ int load(const DmCache& d, uint32_t row, RowSlot& s) const {
         s.row = row;
         s.missed = false;
         if (!PRESENT) return gload(row);
+        if (PIN) {
+            const uint32_t r = row & 0xffu;     // [one (plane, context) block][rank of prev]: the low byte is the rank
+            if (r < d.mask) { s.addr = d.data_off + (r << 5); return (int)lds_read16(s.addr); }
+            s.addr = kNotInLds;
+            s.missed = ASYNC;
+            return ASYNC ? gload_async(row) : gload(row);
+        }
         const uint32_t set = (row ^ (row >> d.shift)) & d.mask;
         if (!TWOWAY) {
             s.addr = d.data_off + (set << 5);
@@ -135,14 +150,15 @@ struct Table2 {
         if (ntp != tp) lds_write32(taddr, ntp);
         return v;
     }
-    template <bool PRESENT>
+    template <bool PRESENT, bool PIN = false>
     __device__ __forceinline__ void store(const DmCache& d, const RowSlot& s, int v) const {
-        if (!PRESENT) gstore(s.row, v);
+        if (!PRESENT || (PIN && s.addr == kNotInLds)) gstore(s.row, v);
         else lds_write16(s.addr, (uint32_t)v);
     }
-    template <bool PRESENT, bool TWOWAY>
+    template <bool PRESENT, bool TWOWAY, bool PIN = false>
     __device__ __forceinline__ void reset(const DmCache& d, int li) const {
         if (!PRESENT) return;
+        if (PIN) { for (uint32_t r = 0; r < d.mask; ++r) lds_write16(d.data_off + (r << 5), 4u * (uint32_t)li + 4u); return; }   // the default CDF
         if (TWOWAY) { for (uint32_t s = (uint32_t)li; s <= d.mask; s += 16u) lds_write32(d.tag_off + (s << 2), 0x3fffffffu); }
         else { for (uint32_t s = (uint32_t)li; s <= d.mask; s += 16u) lds_write16(d.tag_off + (s << 1), 0x7fffu); }
     }
@@ -160,6 +176,7 @@ __device__ __forceinline__ void pad_valu(int& x) {
 struct Caches { DmCache hs, hc, ls, lc; };   // high stride rows, high context-map rows (FirstNibble), low stride rows, low context-map rows
 // which of them exist is a compile-time mask CM (an absent cache then costs no registers): bit 0 hs, 1 hc, 2 ls, 3 lc
 constexpr int CM_HS = 1, CM_HC = 2, CM_LS = 4, CM_LC = 8, CM_2WAY = 16;   // CM_2WAY: the organisation of all of them
+constexpr int CM_PIN = 32;   // the high stride rows are pinned by rank (with CM_HS alone, MM == 4, CTXC, no mixing, no segment lists)
 
 __device__ __forceinline__ uint32_t dm_rows(uint32_t packed, int i) { return (packed >> (8 * i)) & 0xffu; }   // log2(rows) + 1, 0 = absent
 
@@ -183,6 +200,14 @@ __device__ __forceinline__ Caches make_caches(const LitBatch& b, uint32_t stream
         all[i]->tag_off = off;
         off += rows * 2u;
     }
+    return c;
+}
+
+// pinned organisation: [ring][P slots of 32 bytes], P = what the stream's share of the LDS holds (lit_decode2_stream_lds)
+__device__ __forceinline__ Caches make_pinned(const LitBatch& b, uint32_t stream_base, int li) {
+    Caches c = {};
+    c.hs.data_off = stream_base + kRingBytes + 2u * (uint32_t)li;
+    c.hs.mask = (b.cache_bytes_per_wg / (LIT_THREADS / 16) - kRingBytes) >> 5;
     return c;
 }
 
@@ -314,7 +339,7 @@ __device__ __forceinline__ void scaled_pair2(int cv, const Searched& s, int rbas
 }
 
 // sym_to_start_and_freq for the searched symbol under the row `cv`, state update, blend and store: the non-mixing nibble
-template <bool PRESENT>
+template <bool PRESENT, bool PIN = false>
 __device__ __forceinline__ void finish2(const Table2& tb, const DmCache& dc, int li1, int rbase4, const RowSlot& slot_ref, int value,
                                         bool is_default, int cv, const Searched& s, uint32_t slot, uint64_t& S, int inc, int lim) {
     uint32_t dsym, dpsym;
@@ -322,7 +347,7 @@ __device__ __forceinline__ void finish2(const Table2& tb, const DmCache& dc, int
     advance_state(S, slot, dsym, dpsym);
     int st = value;
     if (!is_default) st = blend2(st, li1, s.above, inc, lim, s.mx);     // cv == value here, so mx is its total and `above` its predicate
-    tb.template store<PRESENT>(dc, slot_ref, st);
+    tb.template store<PRESENT, PIN>(dc, slot_ref, st);
 }
 
 // The mixing nibble's three (start, freq) pairs -- the symbol under the mixed row p, under the context-map row and under the
@@ -399,7 +424,7 @@ __device__ __forceinline__ Fetched2 fetch2(const LitGeometry& g, const LdsView& 
                                            const History<NEED8>& hist, uint32_t hi_nib) {
     const RowSel rs = select_rows2<HIGH, MM, NEED8>(g, lv.mix, ctx, hist, hi_nib);
     Fetched2 f;
-    f.value = tb.template load<(CM & (HIGH ? CM_HS : CM_LS)) != 0, (CM & CM_2WAY) != 0, HIGH && DIVANS_D2_ASYNC>(HIGH ? cc.hs : cc.ls, rs.stride_row, f.ref);
+    f.value = tb.template load<(CM & (HIGH ? CM_HS : CM_LS)) != 0, (CM & CM_2WAY) != 0, HIGH && DIVANS_D2_ASYNC, HIGH && (CM & CM_PIN) != 0>(HIGH ? cc.hs : cc.ls, rs.stride_row, f.ref);
     f.is_default = (MM < 0 || MM == 2) && rs.is_default;
     return f;
 }
@@ -416,7 +441,7 @@ __device__ __forceinline__ void init_table2(const Table2& t, const Caches& cc, u
         if (i + 16u * (uint32_t)li < rows * 32u) __builtin_amdgcn_raw_buffer_store_b128(v, t.rsrc, base + i, 0, 0);
     }
     constexpr bool W2 = (CM & CM_2WAY) != 0;
-    t.template reset<(CM & CM_HS) != 0, W2>(cc.hs, li); t.template reset<(CM & CM_HC) != 0, W2>(cc.hc, li);
+    t.template reset<(CM & CM_HS) != 0, W2, (CM & CM_PIN) != 0>(cc.hs, li); t.template reset<(CM & CM_HC) != 0, W2>(cc.hc, li);
     t.template reset<(CM & CM_LS) != 0, W2>(cc.ls, li); t.template reset<(CM & CM_LC) != 0, W2>(cc.lc, li);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_waitcnt(0);  // the row loads that follow must see the fill
@@ -450,7 +475,8 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
         __syncthreads();
     }
     const uint32_t stream_base = lds_base + (threadIdx.x >> 4) * (b.cache_bytes_per_wg / (LIT_THREADS / 16));
-    const Caches cc = make_caches<(CM & CM_2WAY) != 0>(b, stream_base, li);
+    static_assert(!(CM & CM_PIN) || ((CM & ~CM_PIN) == CM_HS && MM == 4 && CTXC && !MIX && !SEG), "pinned high rows: the plain stride-1 decoder under a constant context");
+    const Caches cc = (CM & CM_PIN) ? make_pinned(b, stream_base, li) : make_caches<(CM & CM_2WAY) != 0>(b, stream_base, li);
     MixLanes ml;
     // the same assignment as MixLanes::set (the selftest interpreter's copy): change both together
     ml.odd = (li & 1) != 0; ml.is_p = li < 4; ml.is_cm = (li & 12) == 4; ml.addr_bias = ml.odd ? -4 : 0;
@@ -529,7 +555,7 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
                         const Searched sh = search2(cvh, slot_a, rbase);
                         const uint32_t hi = (uint32_t)sh.sym;
                         const Fetched2 rowL = fetch2<false, MM, NEED8, CM>(g, lv, tb, cc, ctx_cur, hist, hi);
-                        finish2<(CM & CM_HS) != 0>(tb, cc.hs, li1, rbase4, rowH.ref, rowH.value, rowH.is_default, cvh, sh, slot_a, SA, g.inc0, g.lim0);
+                        finish2<(CM & CM_HS) != 0, (CM & CM_PIN) != 0>(tb, cc.hs, li1, rbase4, rowH.ref, rowH.value, rowH.is_default, cvh, sh, slot_a, SA, g.inc0, g.lim0);
                         if (SB < (1ull << 31)) SB = (SB << 32) | ww.next(li);
                         const int cvl = rowL.is_default ? 4 * li1 : rowL.value;
                         const uint32_t slot_b = (uint32_t)SB & 0x7fffu;
@@ -691,8 +717,9 @@ __device__ __forceinline__ void replay_body(const LitBatch& b, uint8_t* lds) {
         __syncthreads();
     }
     const uint32_t stream_base = lds_base + (threadIdx.x >> 4) * (b.cache_bytes_per_wg / (LIT_THREADS / 16));
-    const Caches cc = make_caches<(CM & CM_2WAY) != 0>(b, stream_base, li);
-    constexpr bool W2 = (CM & CM_2WAY) != 0;
+    static_assert(!(CM & CM_PIN) || ((CM & ~CM_PIN) == CM_HS && CTXC && !MIX), "pinned high rows: as decode2_body");
+    const Caches cc = (CM & CM_PIN) ? make_pinned(b, stream_base, li) : make_caches<(CM & CM_2WAY) != 0>(b, stream_base, li);
+    constexpr bool W2 = (CM & CM_2WAY) != 0, PIN = (CM & CM_PIN) != 0;
     constexpr bool HS_C = (CM & CM_HS) != 0, HC_C = (CM & CM_HC) != 0, LS_C = (CM & CM_LS) != 0, LC_C = (CM & CM_LC) != 0;
     for (uint32_t s = gg; s < b.n_streams; s += G) {
         const uint32_t len = b.in_sizes ? b.in_sizes[s] : b.stream_len;
@@ -710,7 +737,7 @@ __device__ __forceinline__ void replay_body(const LitBatch& b, uint8_t* lds) {
         {
             const RowSel rh = select_rows2<true, MM, false>(g, lv.mix, ctx_cur, hist, 0u);
             const RowSel rl = select_rows2<false, MM, false>(g, lv.mix, ctx_cur, hist, cur >> 4);
-            hs_v = tb.template load<HS_C, W2, false>(cc.hs, rh.stride_row, hs_ref);
+            hs_v = tb.template load<HS_C, W2, false, PIN>(cc.hs, rh.stride_row, hs_ref);
             if (MIX) hc_v = tb.template load<HC_C, W2, false>(cc.hc, rh.cm_row, hc_ref);
             ls_v = tb.template load<LS_C, W2, false>(cc.ls, rl.stride_row, ls_ref);
             if (MIX) lc_v = tb.template load<LC_C, W2, false>(cc.lc, rl.cm_row, lc_ref);
@@ -726,7 +753,7 @@ __device__ __forceinline__ void replay_body(const LitBatch& b, uint8_t* lds) {
                 {
                     const bool above = (uint32_t)li >= hi;
                     const int st = blend2(hs_v, li1, above, g.inc0, g.lim0, row_bcast<15>(hs_v));
-                    tb.template store<HS_C>(cc.hs, hs_ref, st);
+                    tb.template store<HS_C, PIN>(cc.hs, hs_ref, st);
                     if (MIX) { const int cm = blend2(hc_v, li1, above, g.inc3, g.lim3, row_bcast<15>(hc_v)); tb.template store<HC_C>(cc.hc, hc_ref, cm); }
                 }
                 hist.push(cur, PERM);
@@ -736,7 +763,7 @@ __device__ __forceinline__ void replay_body(const LitBatch& b, uint8_t* lds) {
                 const RowSel rh = select_rows2<true, MM, false>(g, lv.mix, ctx_cur, hist, 0u);
                 const RowSel rl = select_rows2<false, MM, false>(g, lv.mix, ctx_cur, hist, nxt >> 4);
                 RowSlot nhs = {}, nhc = {}, nls = {}, nlc = {};
-                const int nhs_v = tb.template load<HS_C, W2, false>(cc.hs, rh.stride_row, nhs);
+                const int nhs_v = tb.template load<HS_C, W2, false, PIN>(cc.hs, rh.stride_row, nhs);
                 int nhc_v = 0; if (MIX) nhc_v = tb.template load<HC_C, W2, false>(cc.hc, rh.cm_row, nhc);
                 // low nibble of the byte in hand
                 {
@@ -818,7 +845,18 @@ static LitKernel pick_decode2_w(bool mix, bool seg, uint32_t cm, int mm, bool ct
     if (cm == (uint32_t)(CM_HS | CM_LS)) return pick_decode2_cm<false, false, CM_HS | CM_LS | W2>(mm, ctxc);
     return cm ? pick_decode2_cm<false, false, CM_HS | W2>(mm, ctxc) : pick_decode2_cm<false, false, 0>(mm, ctxc);
 }
-static LitKernel pick_decode2(bool mix, bool seg, uint32_t cm, bool two_way, int mm, bool ctxc) {
+// the pinned organisation of the high stride rows exists for the plain stride-1 decoder under a constant context, high-row cache only
+static bool pinned_instance(bool mix, bool seg, uint32_t cm, int mm, bool ctxc) { return !mix && !seg && cm == (uint32_t)CM_HS && mm == 4 && ctxc; }
+
+static LitKernel pick_decode2(bool mix, bool seg, uint32_t cm, bool two_way, bool pinned, int mm, bool ctxc) {
+    if (pinned) {
+        if (!pinned_instance(mix, seg, cm, mm, ctxc)) return nullptr;
+#if DIVANS_D2_W7
+        return lit_decode2_kernel_w7<4, true, false, false, CM_HS | CM_PIN>;
+#else
+        return lit_decode2_kernel_any<4, true, false, false, CM_HS | CM_PIN>;
+#endif
+    }
     return two_way ? pick_decode2_w<CM_2WAY>(mix, seg, cm, mm, ctxc) : pick_decode2_w<0>(mix, seg, cm, mm, ctxc);
 }
 
@@ -844,10 +882,16 @@ uint32_t lit_lds_bytes2(const LitBatch& b) {
     return bytes;
 }
 
-uint32_t lit_decode2_stream_lds(uint32_t dm_log2) {
+uint32_t lit_decode2_stream_lds(uint32_t dm_log2, bool pinned) {
     uint32_t rows = 0;
     for (int i = 0; i < 4; ++i) { const uint32_t lg = (dm_log2 >> (8 * i)) & 0xffu; rows += lg ? 1u << (lg - 1u) : 0u; }
+    // pinned: no tags, so what `rows` tagged rows take holds rows * 34 / 32 slots of 32 bytes (32 -> 34, 64 -> 68); a rank is below 256
+    if (pinned) return kRingBytes + std::min(rows * 34u / 32u, 256u) * 32u;
     return kRingBytes + rows * 34u;
+}
+
+bool lit_decode2_can_pin(const LitBatch& b, bool mix) {
+    return pinned_instance(mix, b.segs != nullptr, wanted_cache_mask(b.dm_log2), b.geom.mm_uniform, b.geom.ctx_const >= 0);
 }
 
 // The instance launch_decode2 picks, spelt the way rocprofv3 reports it (so that a bench line and a kernel trace name the same thing)
@@ -857,7 +901,8 @@ void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap)
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     const int w2 = (b.dm_shift >> 31) ? CM_2WAY : 0;
     int cmv;
-    if (mix) cmv = (!seg && cm == (uint32_t)(CM_HS | CM_HC | CM_LC)) ? (CM_HS | CM_HC | CM_LC | w2) : (cm ? (CM_HS | CM_HC | w2) : 0);
+    if (b.dm_shift & LIT_DM_PINNED) cmv = CM_HS | CM_PIN;
+    else if (mix) cmv = (!seg && cm == (uint32_t)(CM_HS | CM_HC | CM_LC)) ? (CM_HS | CM_HC | CM_LC | w2) : (cm ? (CM_HS | CM_HC | w2) : 0);
     else cmv = (!seg && cm == (uint32_t)(CM_HS | CM_LS)) ? (CM_HS | CM_LS | w2) : (cm ? (CM_HS | w2) : 0);
     snprintf(buf, cap, "divans_hip::lit_decode2_kernel_%s<%d, %s, %s, %s, %d>", (mm >= 0 && DIVANS_D2_W7) ? "w7" : "any", mm,
              ctxc ? "true" : "false", mix ? "true" : "false", seg ? "true" : "false", cmv);
@@ -867,7 +912,8 @@ hipError_t launch_decode2(const LitBatch& b, bool mix, uint32_t blocks, hipStrea
     const int mm = (b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4) ? b.geom.mm_uniform : -1;
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     if (cm != supported_cache_mask(mix, b.segs != nullptr, cm)) return hipErrorInvalidValue;   // the host passes lit_decode2_effective_caches()
-    LitKernel k = pick_decode2(mix, b.segs != nullptr, cm, (b.dm_shift >> 31) != 0u, mm, b.geom.ctx_const >= 0);
+    LitKernel k = pick_decode2(mix, b.segs != nullptr, cm, (b.dm_shift >> 31) != 0u, (b.dm_shift & LIT_DM_PINNED) != 0u, mm, b.geom.ctx_const >= 0);
+    if (!k) return hipErrorInvalidValue;      // the host asks lit_decode2_can_pin() first
     const uint32_t lds = lit_lds_bytes2(b);
     if (lds > 65536u) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(LIT_THREADS), lds, st, b);
@@ -890,7 +936,9 @@ hipError_t launch_row_replay(const LitBatch& b, bool mix, uint32_t blocks, hipSt
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     const bool two_way = (b.dm_shift >> 31) != 0u, ctxc = b.geom.ctx_const >= 0;
     LitKernel k = nullptr;
-    if (!mix && cm == (uint32_t)CM_HS) {
+    if (b.dm_shift & LIT_DM_PINNED) {
+        if (pinned_instance(mix, false, cm, 4, ctxc)) k = row_replay_kernel<true, false, CM_HS | CM_PIN>;
+    } else if (!mix && cm == (uint32_t)CM_HS) {
         if (ctxc) k = two_way ? row_replay_kernel<true, false, CM_HS | CM_2WAY> : row_replay_kernel<true, false, CM_HS>;
         else k = two_way ? row_replay_kernel<false, false, CM_HS | CM_2WAY> : row_replay_kernel<false, false, CM_HS>;
     } else if (mix && cm == (uint32_t)(CM_HS | CM_HC)) {

@@ -62,7 +62,9 @@ struct LitBatch {
     uint32_t* status;           // device word: bit 0 = encoder saw an invalid (start,freq), bit 1 = decoder integrity check failed
     // lit_decode2.hip: four direct-mapped row caches per stream (high stride rows, high context-map rows, low stride rows, low
     // context-map rows), one byte each: log2(rows) + 1, 0 = that table is not cached; and the hash shift of each
-    // (set = (row ^ (row >> shift)) & (rows - 1)).  cache_bytes_per_wg then covers the word rings too.
+    // (set = (row ^ (row >> shift)) & (rows - 1)).  cache_bytes_per_wg then covers the word rings too.  Bit 31 of dm_shift selects the
+    // 2-way organisation of all four, LIT_DM_PINNED the pinned organisation of the high stride rows (lit_decode2_can_pin): the rows of
+    // the byte ranks 0 .. P-1 live in LDS, P = what cache_bytes_per_wg leaves a stream behind its ring / 32.
     uint32_t dm_log2, dm_shift;
     uint8_t* stream_bad;        // optional [n_streams]: set to 1 for every stream whose decode failed its integrity check
     // lit_model_encode_kernel, one stream coded piece by piece (divans_gpu_lit_stream_*): `resume` = this launch continues the
@@ -78,7 +80,8 @@ struct LitBatch {
     // numeric.  A private layout of the launch: any order decodes the same bytes.
     const uint8_t* byte_rank;
 };
-constexpr uint32_t LIT_STATUS_BAD_MODEL = 1u;     // rANS pass: freq == 0 or start/freq outside 15 bits
+constexpr uint32_t LIT_DM_PINNED = 1u << 30;
+constexpr uint32_t LIT_STATUS_BAD_MODEL = 1u;    // rANS pass: freq == 0 or start/freq outside 15 bits
 constexpr uint32_t LIT_STATUS_BAD_SEGMENT = 4u;   // a segment names a literal block type outside the codec's context tables, or a stream's segment lengths do not add up to it
 constexpr uint32_t LIT_STATUS_OUTPUT_FULL = 8u;   // divans_gpu_lit_encode_packed: the coded streams did not fit the caller's buffer
 constexpr uint32_t LIT_STATUS_BAD_STREAM = 2u;    // decode: a chunk did not end with both states at 2^31, or the coded words were not consumed exactly
@@ -191,7 +194,8 @@ hipError_t launch_decode2(const LitBatch& b, bool mix, uint32_t blocks, hipStrea
 void lit_decode_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);    // the instances the two launchers pick, as rocprofv3 spells them
 void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);
 uint32_t lit_decode2_effective_caches(uint32_t dm_log2, bool mix, bool seg);   // the caches of dm_log2 a kernel instance exists for
-uint32_t lit_decode2_stream_lds(uint32_t dm_log2);   // LDS bytes one stream takes in lit_decode2_kernel (word ring + row caches)
+uint32_t lit_decode2_stream_lds(uint32_t dm_log2, bool pinned = false);   // LDS bytes one stream takes in lit_decode2_kernel (word ring + row caches: 34 bytes per tagged row, 32 per pinned one)
+bool lit_decode2_can_pin(const LitBatch& b, bool mix);    // a pinned instance exists for this launch (b.geom, b.segs and b.dm_log2 are read)
 // Decoders that lost their measurement and are NOT part of the default library (build with DIVANS_WITH_EXPERIMENTAL_DECODERS=1 in the
 // environment of divans_amd/build.py to have them): generation 4 = lit_decode_t.hip, one lane per stream, 30-45 % slower everywhere
 // (profiles/r04e_lane_per_stream_decoder.txt), and the instances of generation 1's lit_decode_kernel no product path needs (the unified and

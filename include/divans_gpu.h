@@ -287,6 +287,18 @@ int divans_gpu_codec_set_bucket_batch(divans_gpu_codec *c, uint32_t streams);
  * call-by-call stream decoder); there divans_gpu_codec_set_geometry / _set_split_cache only shape the streaming encoder pass. */
 int divans_gpu_codec_set_decoder(divans_gpu_codec *c, uint32_t generation, const uint32_t rows[4], const uint32_t shifts[4],
                                  uint32_t blocks);
+/* Tuning: a third organisation of the high stride rows, for the plain stride-1 decoder under a constant context (divans_lit_config_simple
+ * and the like; generations 2 / 3, high-row cache only, calls without a segment list).  PINNED: the rows of the previous bytes of rank
+ * 0 .. P-1 in the byte order (divans_gpu_codec_set_byte_order) live in LDS for a whole stream, every other high row is read from and
+ * written to the table in memory like a low row; no tags, so the LDS of 32 / 64 tagged rows holds P = 34 / 68.  A rare byte then evicts
+ * nobody (text: 3.6-8.1 instead of 7.2-12.6 % of a stream's high rows go to memory).
+ *   0 (default) = by the byte order: pinned once a rank that orders by frequency is in use (the learned order after the first batch, or
+ *       the English hint) and nobody chose an organisation with divans_gpu_codec_set_decoder; tagged caches otherwise.
+ *   1 = never: the direct-mapped / 2-way caches.
+ *   2 = wherever a pinned instance exists, whatever the order (numeric order pins the byte values 0 .. P-1).
+ * The pinned set is the codec's, not a stream's: a batch whose streams' alphabets differ from the rank the codec learned loses what
+ * the tagged caches would have adapted to -- such a caller sets 1.  The decoded bytes do not depend on it. */
+int divans_gpu_codec_set_high_row_pinning(divans_gpu_codec *c, uint32_t mode);
 /* The rANS pass of streams of at most two 65 536-symbol chunks: 1 = one lane per chunk, 2 = two lanes per chunk, one per rANS state
  * (ans.rs:302-329: the states alternate symbol by symbol and only share the output order), 0 = automatic (default): two lanes while
  * that still gives every SIMD at most one wave -- batches up to 64 streams per CU, where it halves the pass (a lane's chain is half as

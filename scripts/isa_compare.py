@@ -7,7 +7,7 @@ LDS, scratch, spills and place in the file.  Cross-compiles only; no GPU.
 
 Both trees' sources (build.py's SOURCES that end in .hip; one the other tree lacks is listed with its figures) are compiled with
 build.py's FLAGS plus -S --cuda-device-only.  Comments and
-the .file / .ident / .loc lines are dropped; what is left of a kernel's body (instructions, labels, directives) is compared as text.
+the .file / .ident / .loc lines are dropped and local labels lose the ordinal of their function; what is left of a kernel's body (instructions, labels, directives) is compared as text.
 The figures come from the kernels' metadata records at the end of the assembly."""
 import os
 import re
@@ -32,7 +32,8 @@ def assembly(tree, src, tmp, tag):
     for l in open(out):
         l = re.split(r";|//", l, 1)[0].rstrip()
         if l.strip() and not re.match(r"\s*\.(file|ident|loc)\b", l):
-            lines.append(l)
+            # local labels carry the ordinal of their function in the file (.LBB12_3): a kernel added in front renumbers the ones behind it
+            lines.append(re.sub(r"\.L(BB|JTI|CPI)\d+_", r".L\1_", l))
     return lines
 
 
