@@ -210,6 +210,11 @@ def load_library():
     L.divans_ir_num_block_types.argtypes = [vp]; L.divans_ir_num_block_types.restype = u32
     L.divans_ir_expand.argtypes = [vp, vp, sz]
     L.divans_ir_literal_segments.argtypes = [vp, vp, sz, vp, sz]
+    L.divans_gpu_lit_decode_commands_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.divans_gpu_codec_set_stream_flags.argtypes = [vp, vp]
+    for name in ("divans_ir_num_device_commands", "divans_ir_insert_size"):
+        getattr(L, name).argtypes = [vp]; getattr(L, name).restype = sz
+    L.divans_ir_device_commands.argtypes = [vp, vp, sz, vp, sz]
     L.divans_ir_options_default.argtypes = [ctypes.POINTER(IrOptions)]
     L.divans_ir_options_default.restype = None
     L.divans_ir_lit_config.argtypes = [vp, ctypes.POINTER(IrOptions), ctypes.POINTER(LitConfig)]
@@ -236,7 +241,7 @@ def exported_symbols():
         "divans_gpu_lit_encode_host", "divans_gpu_lit_encode_host_chunks", "divans_gpu_lit_decode_host", "divans_gpu_codec_info",
         "divans_gpu_codec_set_geometry", "divans_gpu_codec_set_split_cache", "divans_gpu_codec_tune_tables", "divans_gpu_codec_search_tables", "divans_gpu_codec_table_placement", "divans_gpu_table_memory", "divans_gpu_set_table_va_cap", "divans_gpu_trim", "divans_gpu_codec_set_decoder", "divans_gpu_codec_set_high_row_pinning", "divans_gpu_experimental_decoders", "divans_gpu_codec_set_byte_order", "divans_gpu_codec_byte_order", "divans_gpu_codec_row_replay", "divans_gpu_codec_set_rans_split", "divans_gpu_codec_set_encode_path", "divans_gpu_codec_last_encode_path", "divans_gpu_codec_set_bucket_batch", "divans_gpu_codec_high_row_slots", "divans_gpu_codec_bucket_stride", "divans_gpu_lit_model_batch",
         "divans_gpu_selftest_division", "divans_gpu_speed_supported", "divans_gpu_speed_accepted", "divans_gpu_codec_status", "divans_gpu_codec_clear_status", "divans_gpu_codec_status_async", "divans_gpu_codec_last_decode_kernel", "divans_gpu_codec_set_stream_flags", "divans_gpu_codec_set_block_types",
-        "divans_gpu_lit_encode_segments_batch", "divans_gpu_lit_decode_segments_batch",
+        "divans_gpu_lit_encode_segments_batch", "divans_gpu_lit_decode_segments_batch", "divans_gpu_lit_decode_commands_batch",
         "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_cdf_ops_on", "divans_gpu_selftest_rans_pairs", "divans_gpu_selftest_rans_batch", "divans_gpu_lit_encode_batch_chunks",
         "divans_gpu_lit_encode_host_pipelined", "divans_gpu_lit_decode_host_pipelined", "divans_gpu_host_alloc", "divans_gpu_host_free",
         "divans_gpu_lit_stream_begin", "divans_gpu_lit_stream_encode", "divans_gpu_lit_stream_finish",
@@ -254,7 +259,18 @@ def exported_ir_symbols():
     """Entry points include/divans_ir.h declares."""
     return ["divans_ir_parse", "divans_ir_free", "divans_ir_num_commands", "divans_ir_count", "divans_ir_raw_size", "divans_ir_expand",
             "divans_ir_literal_size", "divans_ir_num_segments", "divans_ir_num_block_types", "divans_ir_literal_segments",
+            "divans_ir_num_device_commands", "divans_ir_insert_size", "divans_ir_device_commands",
             "divans_ir_options_default", "divans_ir_lit_config"]
+
+
+class LitCommand(ctypes.Structure):
+    """divans_lit_command"""
+    _fields_ = [("kind", ctypes.c_uint32), ("len", ctypes.c_uint32), ("arg", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+CMD_COPY, CMD_INSERT, CMD_LITERAL = 0, 1, 3
+CMD_DTYPE = np.dtype([("kind", "<u4"), ("len", "<u4"), ("arg", "<u4"), ("reserved", "<u4")])      # divans_lit_command
+STATUS_BAD_COMMAND = 16      # DIVANS_GPU_STATUS_BAD_COMMAND
 
 
 class CommandIR:
@@ -302,6 +318,15 @@ class CommandIR:
         segs = np.zeros(max(k, 1), dtype=np.dtype([("len", "<u4"), ("btype", "<u4"), ("last8", "<u8")]))
         _check(self._lib.divans_ir_literal_segments(self._h, lit.ctypes.data, n, segs.ctypes.data, k), "divans_ir_literal_segments")
         return lit[:n], segs[:k]
+
+    def device_commands(self):
+        """(commands structured array with fields kind / len / arg / reserved -- the divans_lit_command records of
+        divans_gpu_lit_decode_commands_batch --, insert bytes uint8[m]): what a decompressor hands the GPU"""
+        k = int(self._lib.divans_ir_num_device_commands(self._h)); m = int(self._lib.divans_ir_insert_size(self._h))
+        cmds = np.zeros(max(k, 1), dtype=CMD_DTYPE)
+        ins = np.empty(max(m, 1), dtype=np.uint8)
+        _check(self._lib.divans_ir_device_commands(self._h, cmds.ctypes.data, k, ins.ctypes.data, m), "divans_ir_device_commands")
+        return cmds[:k], ins[:m]
 
     def lit_config(self, **options):
         o = IrOptions()
@@ -606,6 +631,21 @@ class LiteralCodec:
         _check(self._lib.divans_gpu_lit_decode_segments_batch(
             self._h, d_coded.data_ptr(), d_offsets.data_ptr(), d_sizes.data_ptr(), int(n_streams), seg_begin.data_ptr(), segs.data_ptr(),
             d_out.data_ptr(), out_offsets.data_ptr(), out_sizes.data_ptr(), int(stream_len)), "divans_gpu_lit_decode_segments_batch")
+
+    def decode_commands_batch(self, d_coded, d_offsets, d_sizes, n_streams, cmd_begin, cmds, lit_sizes, lit_stream_len, d_raw, raw_offsets,
+                              raw_sizes, ins=None, ins_offsets=None, ins_sizes=None):
+        """General streams from their command lists (device tensors: cmd_begin int32[n+1], cmds uint8 view of the 16-byte
+        divans_lit_command records, lit_sizes int32[n]; ins / ins_offsets / ins_sizes all None when no stream has an INSERT command):
+        the kernel runs the Copy / Insert commands itself and writes every stream's raw bytes at raw_offsets[i]."""
+        p = lambda t: t.data_ptr() if t is not None else None
+        _check(self._lib.divans_gpu_lit_decode_commands_batch(
+            self._h, d_coded.data_ptr(), d_offsets.data_ptr(), d_sizes.data_ptr(), int(n_streams), cmd_begin.data_ptr(), cmds.data_ptr(),
+            lit_sizes.data_ptr(), int(lit_stream_len), p(ins), p(ins_offsets), p(ins_sizes), d_raw.data_ptr(), raw_offsets.data_ptr(),
+            raw_sizes.data_ptr()), "divans_gpu_lit_decode_commands_batch")
+
+    def set_stream_flags(self, d_flags):
+        """a device uint8 tensor (>= n_streams, zeroed by the caller) that receives a 1 for every stream a decode call reports, or None"""
+        _check(self._lib.divans_gpu_codec_set_stream_flags(self._h, d_flags.data_ptr() if d_flags is not None else None), "divans_gpu_codec_set_stream_flags")
 
     def stream_encode_pieces(self, pieces):
         """One stream handed over piece by piece (divans_gpu_lit_stream_*): returns (coded bytes, chunk sizes)."""

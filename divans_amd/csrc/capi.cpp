@@ -1453,6 +1453,53 @@ extern "C" int divans_gpu_lit_decode_segments_batch(divans_gpu_codec* c, const u
     return decode_batch_impl(c, d_in, d_in_offsets, d_in_sizes, n_streams, d_out, d_out_offsets, d_out_sizes, stream_len, d_seg_begin, d_segs);
 }
 
+static_assert(sizeof(divans_lit_command) == sizeof(LitCommand) && sizeof(LitCommand) == 16, "divans_lit_command is the kernels' LitCommand");
+static_assert(DIVANS_CMD_COPY == LIT_CMD_COPY && DIVANS_CMD_INSERT == LIT_CMD_INSERT && DIVANS_CMD_LITERAL == LIT_CMD_LITERAL, "command kinds");
+static_assert(DIVANS_GPU_STATUS_BAD_COMMAND == LIT_STATUS_BAD_COMMAND, "status bits");
+
+// General streams decoded from their command lists: one launch of a lit_decode2_cmd_kernel instance, which runs the Copy / Insert
+// commands itself.  The launch is of another shape than any divans_gpu_lit_decode_batch call (raw output, its own kernels): it decodes on
+// the table placement in use and is never one of the placement search's measurements.
+extern "C" int divans_gpu_lit_decode_commands_batch(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                                    const uint32_t* d_in_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                                    const divans_lit_command* d_cmds, const uint32_t* d_lit_sizes, uint32_t lit_stream_len,
+                                                    const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                                    uint8_t* d_raw, const uint64_t* d_raw_offsets, const uint32_t* d_raw_sizes) {
+    if (!c || !d_in || !d_in_offsets || !d_in_sizes || !d_cmd_begin || !d_cmds || !d_lit_sizes || !d_raw || !d_raw_offsets || !d_raw_sizes)
+        return fail(DIVANS_GPU_EINVAL, "null argument");
+    if ((d_ins == nullptr) != (d_ins_offsets == nullptr) || (d_ins == nullptr) != (d_ins_sizes == nullptr))
+        return fail(DIVANS_GPU_EINVAL, "insert bytes, their offsets and their sizes go together");
+    if (lit_stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "lit_stream_len exceeds the codec's max_stream_len");
+    if (!use_decode2(c)) return fail(DIVANS_GPU_EINVAL, "command lists need decoder generation 2 or 3 (this codec decodes with generation 1: a speed whose row totals leave i16, or divans_gpu_codec_set_decoder)");
+    if (c->sp_started || c->sd_started) return fail(DIVANS_GPU_EINVAL, "a stream coded call by call is open on this codec");
+    if (n_streams == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_tables(c); if (rc) return rc;
+    LitBatch b;
+    std::memset(&b, 0, sizeof(b));
+    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
+    b.n_streams = n_streams; b.stream_len = lit_stream_len; b.max_stream_len = c->max_stream_len;
+    b.in = d_in; b.in_offsets = d_in_offsets; b.in_sizes = d_in_sizes;
+    b.out = d_raw; b.out_offsets = d_raw_offsets; b.out_sizes = d_raw_sizes; b.status = c->d_status;
+    b.stream_bad = c->d_stream_flags;
+    b.byte_rank = (c->byte_order != 1u && c->rank_ready) ? c->d_rank : nullptr;
+    // the high-row caches in the 2-way organisation, or none: a subset of what the codec's grid was sized for
+    b.dm_log2 = lit_decode2_commands_caches(c->dm_log2, c->mix, c->geom.total_rows);
+    b.dm_shift = (c->dm_shift & 0x1f1f1f1fu) | 0x80000000u;
+    b.cache_bytes_per_wg = (LIT_THREADS / 16) * lit_decode2_stream_lds(b.dm_log2);
+    c->last_decode_grid = std::min(c->blocks2, (n_streams + groups_per_block(c) - 1u) / groups_per_block(c));
+    LitCommandLists cl;
+    cl.cmd_begin = d_cmd_begin; cl.cmds = (const LitCommand*)d_cmds; cl.lit_sizes = d_lit_sizes;
+    cl.ins = d_ins; cl.ins_offsets = d_ins_offsets; cl.ins_sizes = d_ins_sizes;
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    ++c->table_launch_seq;
+    lit_decode2_commands_kernel_name(b, c->mix, c->last_decode_kernel, sizeof(c->last_decode_kernel));
+    HIP_TRY(launch_decode2_commands(b, cl, c->mix, c->last_decode_grid, c->stream));
+    HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+    c->timing_pending_dec = true;
+    return 0;
+}
+
 // Cache organisation and grid of lit_decode2_kernel for a batch of n_streams (also what divans_gpu_codec_row_replay launches with)
 static void decode2_shape(divans_gpu_codec* c, uint32_t n_streams, bool segs, LitBatch& b, uint32_t& grid) {
     b.dm_log2 = lit_decode2_effective_caches(c->dm_log2, c->mix, segs); b.dm_shift = c->dm_shift;

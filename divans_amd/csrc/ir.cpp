@@ -253,6 +253,34 @@ int divans_ir_literal_segments(const divans_ir* ir, uint8_t* lit, size_t lit_cap
     return walk(ir, raw.data(), lit, segs);
 }
 
+size_t divans_ir_num_device_commands(const divans_ir* ir) {
+    return ir ? ir->counts[DIVANS_IR_LITERAL] + ir->counts[DIVANS_IR_COPY] + ir->counts[DIVANS_IR_DICT] : 0;
+}
+
+size_t divans_ir_insert_size(const divans_ir* ir) {
+    size_t n = 0;
+    if (ir) for (const Cmd& c : ir->cmds) if (c.kind == DIVANS_IR_DICT) n += c.data_len;
+    return n;
+}
+
+int divans_ir_device_commands(const divans_ir* ir, divans_lit_command* cmds, size_t cmd_cap, uint8_t* ins, size_t ins_cap) {
+    const size_t n_cmds = divans_ir_num_device_commands(ir), n_ins = divans_ir_insert_size(ir);
+    if (!ir || (!cmds && n_cmds) || (!ins && n_ins)) return fail("null argument");
+    if (cmd_cap < n_cmds || ins_cap < n_ins) return divans_host::set_last_error(DIVANS_GPU_ECAP, "IR: command / insert buffer too small");
+    size_t k = 0, ipos = 0; uint32_t bt = 0;
+    for (const Cmd& c : ir->cmds) {
+        if (c.kind == DIVANS_IR_LITERAL) cmds[k++] = divans_lit_command{DIVANS_CMD_LITERAL, c.a, bt, 0u};
+        else if (c.kind == DIVANS_IR_COPY) cmds[k++] = divans_lit_command{DIVANS_CMD_COPY, c.a, c.b, 0u};
+        else if (c.kind == DIVANS_IR_DICT) {
+            if (ipos + c.data_len > 0xffffffffull) return fail("more than 4 GiB of dictionary words");
+            cmds[k++] = divans_lit_command{DIVANS_CMD_INSERT, (uint32_t)c.data_len, (uint32_t)ipos, 0u};
+            std::memcpy(ins + ipos, ir->bytes.data() + c.data_off, c.data_len);
+            ipos += c.data_len;
+        } else if (c.kind == DIVANS_IR_BTYPE_LITERAL) bt = c.a;
+    }
+    return 0;
+}
+
 void divans_ir_options_default(divans_ir_options* o) {
     if (!o) return;
     std::memset(o, 0, sizeof(*o));

@@ -449,8 +449,14 @@ __device__ __forceinline__ void init_table2(const Table2& t, const Caches& cc, u
 
 }  // namespace
 
-template <int MM, bool CTXC, bool MIX, bool SEG, int CM>
-__device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
+// LIST: how a stream's literals are split into Literal commands -- LIST_NONE: they are not; LIST_SEGS: by a segment list that
+// carries every command's context (b.segs); LIST_CMDS: by the stream's command list (cl), whose Copy and Insert commands this
+// kernel runs into the stream's raw output itself and whose Literal commands take their context from there (CmdCursor).
+constexpr int LIST_NONE = 0, LIST_SEGS = 1, LIST_CMDS = 2;
+
+template <int MM, bool CTXC, bool MIX, int LIST, int CM>
+__device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, const LitCommandLists& cl) {
+    constexpr bool SEG = LIST == LIST_SEGS, CMD = LIST == LIST_CMDS;
     const LdsView lv = load_config_to_lds<MM, CTXC>(lds, b);
     const LitGeometry& g = b.geom;
     const int lane = threadIdx.x & 63, li = lane & 15, rbase = lane & 48, rbase4 = rbase << 2, li1 = li + 1;
@@ -475,13 +481,13 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
         __syncthreads();
     }
     const uint32_t stream_base = lds_base + (threadIdx.x >> 4) * (b.cache_bytes_per_wg / (LIT_THREADS / 16));
-    static_assert(!(CM & CM_PIN) || ((CM & ~CM_PIN) == CM_HS && MM == 4 && CTXC && !MIX && !SEG), "pinned high rows: the plain stride-1 decoder under a constant context");
+    static_assert(!(CM & CM_PIN) || ((CM & ~CM_PIN) == CM_HS && MM == 4 && CTXC && !MIX && LIST == LIST_NONE), "pinned high rows: the plain stride-1 decoder under a constant context");
     const Caches cc = (CM & CM_PIN) ? make_pinned(b, stream_base, li) : make_caches<(CM & CM_2WAY) != 0>(b, stream_base, li);
     MixLanes ml;
     // the same assignment as MixLanes::set (the selftest interpreter's copy): change both together
     ml.odd = (li & 1) != 0; ml.is_p = li < 4; ml.is_cm = (li & 12) == 4; ml.addr_bias = ml.odd ? -4 : 0;
     for (uint32_t s = gg; s < b.n_streams; s += G) {
-        const uint32_t len = b.out_sizes ? b.out_sizes[s] : b.stream_len;
+        const uint32_t len = CMD ? cl.lit_sizes[s] : (b.out_sizes ? b.out_sizes[s] : b.stream_len);     // literal bytes
         uint8_t* out = b.out + (b.out_offsets ? b.out_offsets[s] : (uint64_t)s * b.stream_len);
         WordRing ww;
         ww.in = (const uint32_t*)(b.in + b.in_offsets[s]);
@@ -498,6 +504,8 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
         uint32_t ctab = LIT_BLOB_CTXF;      // context table of the current literal block type
         SegCursor sc;
         if (SEG) sc.start(b, s, seg_last8, ctab);
+        CmdCursor cx;
+        if (CMD) cx.start(b, cl, s, li, seg_last8, ctab);     // (runs the commands in front of the first literal)
         hist.set(seg_last8, PERM);
         uint32_t k1 = CTXC ? 0u : lv.ctx[LIT_BLOB_LUT1CLASS + hist.p2];   // lut1 class of the byte before the previous one
         uint64_t SA = 0, SB = 0;      // state_a decodes high nibbles, state_b low nibbles (two symbols per byte)
@@ -538,6 +546,9 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
                         if (SEG) {   // the next Literal command starts from the ring buffer's last 8 bytes and its own block type
                             if (--sc.left == 0u) { seg_last8 = hist.last8; sc.advance(g, seg_last8, ctab); hist.set(seg_last8, PERM); }
                         }
+                        if (CMD) {   // the Literal command ends: its bytes go to their places, the commands behind it run, the next one's context is read back
+                            if (cx.take(byte, k, li, outb)) { cx.advance(g, li, seg_last8, ctab); if (cx.live) hist.set(seg_last8, PERM); }
+                        }
                         if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + hist.p2];
                         ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, hist.p1, k1);
                         mrowH = fetch_mix2<true, MM, NEED8, CM>(g, lv, tb, cc, ctx_cur, hist, 0u);   // next byte's rows (harmless past the end)
@@ -545,7 +556,7 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
                         wp.update(li, fh, ph, fl, pl);
                         nh = wp.norm_high(); nl = wp.norm_low();
                         pad_valu<DIVANS_D2_PAD_VALU>(pad);
-                        outb = (uint32_t)li == k ? byte : outb;
+                        if (!CMD) outb = (uint32_t)li == k ? byte : outb;
                     } else {
                         // rowH (this byte's high-nibble row) was requested while the previous byte was being finished
                         if (SA < (1ull << 31)) SA = (SA << 32) | ww.next(li);
@@ -564,21 +575,24 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
                         const uint32_t byte = (hi << 4) | lo;
                         hist.push(byte, PERM);
                         if (SEG) { if (--sc.left == 0u) { seg_last8 = hist.last8; sc.advance(g, seg_last8, ctab); hist.set(seg_last8, PERM); } }
+                        if (CMD) { if (cx.take(byte, k, li, outb)) { cx.advance(g, li, seg_last8, ctab); if (cx.live) hist.set(seg_last8, PERM); } }
                         if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + hist.p2];
                         ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, hist.p1, k1);
                         rowH = fetch2<true, MM, NEED8, CM>(g, lv, tb, cc, ctx_cur, hist, 0u);   // next byte's row (harmless past the end)
                         finish2<(CM & CM_LS) != 0>(tb, cc.ls, li1, rbase4, rowL.ref, rowL.value, rowL.is_default, cvl, sl, slot_b, SB, g.inc0, g.lim0);
                         pad_valu<DIVANS_D2_PAD_VALU>(pad);
-                        outb = (uint32_t)li == k ? byte : outb;
+                        if (!CMD) outb = (uint32_t)li == k ? byte : outb;
                     }
                 }
-                if ((uint32_t)li < cnt) __builtin_nontemporal_store((uint8_t)outb, out + base + li);
+                if (CMD) cx.flush_group(cnt, li, outb);
+                else if ((uint32_t)li < cnt) __builtin_nontemporal_store((uint8_t)outb, out + base + li);
             }
             // rANS is an exact inverse: a chunk that was coded from the start states 2^31 (ans.rs:135-136,331-378) decodes back
             // to exactly those; anything else means a truncated, corrupt or mismatched stream
             corrupt |= (SA != (1ull << 31)) | (SB != (1ull << 31));
         }
         if (SEG && li == 0) sc.finish();
+        if (CMD && li == 0) cx.finish(b, s);
         corrupt |= ww.pos != ww.nwords;     // every coded word consumed, none read past the end
         if (corrupt && li == 0) {
             if (b.status) atomicOr(b.status, LIT_STATUS_BAD_STREAM);
@@ -593,12 +607,19 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds) {
 template <int MM, bool CTXC, bool MIX, bool SEG, int CM>
 __global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(7))) void lit_decode2_kernel_w7(const LitBatch b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    decode2_body<MM, CTXC, MIX, SEG, CM>(b, lds);
+    decode2_body<MM, CTXC, MIX, SEG ? LIST_SEGS : LIST_NONE, CM>(b, lds, LitCommandLists{});
 }
 template <int MM, bool CTXC, bool MIX, bool SEG, int CM>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_kernel_any(const LitBatch b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    decode2_body<MM, CTXC, MIX, SEG, CM>(b, lds);
+    decode2_body<MM, CTXC, MIX, SEG ? LIST_SEGS : LIST_NONE, CM>(b, lds, LitCommandLists{});
+}
+// The command-list instances (LIST_CMDS), kernels of their own so that the ones above keep their names and their code.  They carry
+// the cursor's state on top of the byte loop's and are left to the register count the compiler gives them.
+template <int MM, bool CTXC, bool MIX, int CM>
+__global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_kernel(const LitBatch b, const LitCommandLists cl) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    decode2_body<MM, CTXC, MIX, LIST_CMDS, CM>(b, lds, cl);
 }
 
 
@@ -860,6 +881,22 @@ static LitKernel pick_decode2(bool mix, bool seg, uint32_t cm, bool two_way, boo
     return two_way ? pick_decode2_w<CM_2WAY>(mix, seg, cm, mm, ctxc) : pick_decode2_w<0>(mix, seg, cm, mm, ctxc);
 }
 
+typedef void (*LitCmdKernel)(const LitBatch, const LitCommandLists);
+
+template <bool MIX, int CM>
+static LitCmdKernel pick_decode2_cmd_cm(int mm, bool ctxc) {
+    switch ((mm == 4 ? 2 : (mm == 0 ? 1 : 0)) * 2 + (ctxc ? 1 : 0)) {
+    case 0: return lit_decode2_cmd_kernel<-1, false, MIX, CM>; case 1: return lit_decode2_cmd_kernel<-1, true, MIX, CM>;
+    case 2: return lit_decode2_cmd_kernel<0, false, MIX, CM>;  case 3: return lit_decode2_cmd_kernel<0, true, MIX, CM>;
+    case 4: return lit_decode2_cmd_kernel<4, false, MIX, CM>;  default: return lit_decode2_cmd_kernel<4, true, MIX, CM>;
+    }
+}
+// two cache sets: the high rows (2-way), or none
+static LitCmdKernel pick_decode2_cmd(bool mix, bool cached, int mm, bool ctxc) {
+    if (mix) return cached ? pick_decode2_cmd_cm<true, CM_HS | CM_HC | CM_2WAY>(mm, ctxc) : pick_decode2_cmd_cm<true, 0>(mm, ctxc);
+    return cached ? pick_decode2_cmd_cm<false, CM_HS | CM_2WAY>(mm, ctxc) : pick_decode2_cmd_cm<false, 0>(mm, ctxc);
+}
+
 static uint32_t wanted_cache_mask(uint32_t dm_log2) {
     uint32_t m = 0;
     for (int i = 0; i < 4; ++i) if ((dm_log2 >> (8 * i)) & 0xffu) m |= 1u << i;
@@ -872,6 +909,11 @@ uint32_t lit_decode2_effective_caches(uint32_t dm_log2, bool mix, bool seg) {
     uint32_t out = 0;
     for (int i = 0; i < 4; ++i) if (cm & (1u << i)) out |= dm_log2 & (0xffu << (8 * i));
     return out;
+}
+
+// ... and for a call with a command list: whatever organisation the codec asks for comes down to the high-row caches or none
+uint32_t lit_decode2_commands_caches(uint32_t dm_log2, bool mix, uint32_t total_rows) {
+    return total_rows < 0x7fffu ? lit_decode2_effective_caches(dm_log2, mix, true) : 0u;     // (a tag holds 15 bits of row)
 }
 
 uint32_t lit_lds_bytes2(const LitBatch& b) {
@@ -906,6 +948,24 @@ void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap)
     else cmv = (!seg && cm == (uint32_t)(CM_HS | CM_LS)) ? (CM_HS | CM_LS | w2) : (cm ? (CM_HS | w2) : 0);
     snprintf(buf, cap, "divans_hip::lit_decode2_kernel_%s<%d, %s, %s, %s, %d>", (mm >= 0 && DIVANS_D2_W7) ? "w7" : "any", mm,
              ctxc ? "true" : "false", mix ? "true" : "false", seg ? "true" : "false", cmv);
+}
+
+void lit_decode2_commands_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap) {
+    const int mm = (b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4) ? b.geom.mm_uniform : -1;
+    const int cmv = wanted_cache_mask(b.dm_log2) ? ((mix ? (CM_HS | CM_HC) : CM_HS) | CM_2WAY) : 0;
+    snprintf(buf, cap, "divans_hip::lit_decode2_cmd_kernel<%d, %s, %s, %d>", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false", cmv);
+}
+
+hipError_t launch_decode2_commands(const LitBatch& b, const LitCommandLists& cl, bool mix, uint32_t blocks, hipStream_t st) {
+    const int mm = (b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4) ? b.geom.mm_uniform : -1;
+    const uint32_t cm = wanted_cache_mask(b.dm_log2);
+    // the host passes lit_decode2_commands_caches() and the 2-way organisation; the lists come with raw ranges
+    if (cm != supported_cache_mask(mix, true, cm) || (cm && !(b.dm_shift >> 31)) || (b.dm_shift & LIT_DM_PINNED) || b.segs || !b.out_offsets || !b.out_sizes) return hipErrorInvalidValue;
+    LitCmdKernel k = pick_decode2_cmd(mix, cm != 0u, mm, b.geom.ctx_const >= 0);
+    const uint32_t lds = lit_lds_bytes2(b);
+    if (lds > 65536u) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(LIT_THREADS), lds, st, b, cl);
+    return hipGetLastError();
 }
 
 hipError_t launch_decode2(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st) {

@@ -254,5 +254,128 @@ struct SegCursor {
     }
 };
 
+// Every store issued so far by this wave is complete and visible to the loads that follow (the vector-memory counter covers stores;
+// a workgroup's waves share the CU's L1, which the stores write through): what init_table2 puts between its fill and the row loads.
+__device__ __forceinline__ void drain_stores() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// Walks a stream's command list (general streams decoded from their commands: divans_gpu_lit_decode_commands_batch) and EXECUTES it:
+// the stream's 16 lanes run every Copy and Insert command into the stream's own output, and a Literal command takes its context
+// from the eight bytes in front of it there -- cmd_to_raw/mod.rs:69-86 and codec/mod.rs:771-783 on the device.  `left` = literal
+// bytes of the current Literal command still to decode; advance() is called when it reaches zero, AFTER the caller has stored every
+// literal decoded so far at its place in the output (take()).  All values but `oa` are uniform over the stream's 16 lanes.
+//
+// Every address follows from the command list alone, and every command is checked before it runs: a command that would write
+// past the stream's raw size, read in front of its start or outside its insert bytes, or that names an unknown kind or a block
+// type without a table raises its status bit and ends the walk -- `live` goes false and the stream writes nothing more (the
+// literals that remain are still decoded, under a context that no longer matters, and dropped).
+struct CmdCursor {
+    const LitCommand* cmds; uint32_t idx, end, left;
+    uint32_t pos, rlen;              // bytes of output produced so far, the stream's raw size
+    uint8_t* out;                    // the stream's raw range
+    const uint8_t* ins; uint32_t ins_size;
+    uint32_t flags;                  // status bits this stream raised
+    bool live;                       // a Literal command is open: the literals being decoded belong at out[pos ..]
+    uint32_t oa;                     // per lane: the place in `out` of the literal this lane holds in the byte loop's 16-byte output group
+    uint32_t gstart;                 // the group's first literal that is not stored yet
+
+    // The byte loop has decoded `byte` into lane k of its output group.  True when that ends the Literal command: the literals of
+    // the group that are decoded so far are then stored at their places (a command behind them may read them), and advance() is due.
+    __device__ __forceinline__ bool take(uint32_t byte, uint32_t k, int li, uint32_t& outb) {
+        outb = (uint32_t)li == k ? byte : outb;
+        oa = (uint32_t)li == k ? pos : oa;
+        ++pos;
+        if (--left != 0u) return false;
+        if ((uint32_t)li >= gstart && (uint32_t)li <= k) out[oa] = (uint8_t)outb;
+        gstart = k + 1u;
+        return true;
+    }
+    // The end of an output group of cnt literals: what it still holds belongs to the open Literal command (plain stores: a later
+    // command may read them); after fail() or behind the list's end there is no such command and nothing is written.
+    __device__ __forceinline__ void flush_group(uint32_t cnt, int li, uint32_t outb) {
+        if ((uint32_t)li >= gstart && (uint32_t)li < cnt && live) out[oa] = (uint8_t)outb;
+        gstart = 0u;
+    }
+
+    __device__ __forceinline__ void fail(uint32_t bit) { flags |= bit; live = false; idx = end; }
+
+    // out[pos + j] = out[pos + j - d], j = 0 .. n-1, byte by byte.  An overlapping copy (d < n) repeats the d bytes in front of it, so
+    // EVERY source byte lies in front of the command -- out[pos - d + j % d] -- and the steps need no ordering among themselves.
+    __device__ __forceinline__ void copy(uint32_t n, uint32_t d, int li) {
+        uint8_t* dst = out + pos;
+        const uint8_t* src = dst - d;
+        const bool wraps = d < n;
+        for (uint64_t j0 = (uint64_t)li; j0 < n; j0 += 64u) {      // four loads in flight, then their stores (64-bit: n may be close to 2^32)
+            uint8_t v[4] = {};
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) { const uint64_t j = j0 + 16u * u; if (j < n) v[u] = src[wraps ? (uint32_t)j % d : (uint32_t)j]; }
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) { const uint64_t j = j0 + 16u * u; if (j < n) dst[j] = v[u]; }
+        }
+    }
+    __device__ __forceinline__ void insert(uint32_t n, uint32_t at, int li) {
+        uint8_t* dst = out + pos;
+        const uint8_t* src = ins + at;
+        for (uint64_t j = (uint64_t)li; j < n; j += 16u) dst[j] = src[j];
+    }
+
+    // Runs every command up to the next Literal command with bytes (or to the end of the list), then reads that command's context back:
+    // last8 = the eight bytes in front of it, newest in bits 56..63, zeros in front of the stream's start.
+    __device__ __forceinline__ void advance(const LitGeometry& g, int li, uint64_t& last8, uint32_t& ctab) {
+        live = false;
+        while (left == 0u && idx < end) {
+            const LitCommand c = cmds[idx];
+            ++idx;
+            if (c.kind != LIT_CMD_COPY && c.kind != LIT_CMD_INSERT && c.kind != LIT_CMD_LITERAL) { fail(LIT_STATUS_BAD_COMMAND); break; }
+            if (c.len == 0u) continue;
+            if (c.len > rlen - pos) { fail(LIT_STATUS_BAD_COMMAND); break; }       // pos <= rlen always
+            if (c.kind == LIT_CMD_LITERAL) {
+                const uint32_t t = c.arg - g.bt_first;
+                if (t >= g.n_btypes) { fail(LIT_STATUS_BAD_SEGMENT); break; }
+                ctab = LIT_BLOB_CTXF + t * LIT_CTXF_BYTES;
+                left = c.len;
+                live = true;
+            } else if (c.kind == LIT_CMD_COPY) {
+                if (c.arg == 0u || c.arg > pos) { fail(LIT_STATUS_BAD_COMMAND); break; }
+                drain_stores();          // the bytes it reads: literals, or what the command before it wrote
+                copy(c.len, c.arg, li);
+                pos += c.len;
+            } else {
+                if (c.arg > ins_size || c.len > ins_size - c.arg) { fail(LIT_STATUS_BAD_COMMAND); break; }
+                insert(c.len, c.arg, li);
+                pos += c.len;
+            }
+        }
+        if (!live) return;
+        drain_stores();
+        int v = 0;
+        if (li < 8 && pos >= 8u - (uint32_t)li) v = (int)out[(size_t)pos - 8u + (uint32_t)li];
+        const uint32_t lo = (uint32_t)row_bcast<0>(v) | ((uint32_t)row_bcast<1>(v) << 8) | ((uint32_t)row_bcast<2>(v) << 16) | ((uint32_t)row_bcast<3>(v) << 24);
+        const uint32_t hi = (uint32_t)row_bcast<4>(v) | ((uint32_t)row_bcast<5>(v) << 8) | ((uint32_t)row_bcast<6>(v) << 16) | ((uint32_t)row_bcast<7>(v) << 24);
+        last8 = ((uint64_t)hi << 32) | lo;
+    }
+    __device__ __forceinline__ void start(const LitBatch& b, const LitCommandLists& cl, uint32_t s, int li, uint64_t& last8, uint32_t& ctab) {
+        cmds = cl.cmds; idx = cl.cmd_begin[s]; end = cl.cmd_begin[s + 1]; left = 0u;
+        pos = 0u; rlen = b.out_sizes[s]; out = b.out + b.out_offsets[s];
+        ins = cl.ins ? cl.ins + cl.ins_offsets[s] : nullptr; ins_size = cl.ins ? cl.ins_sizes[s] : 0u;
+        flags = 0u; oa = 0u; gstart = 0u;
+        advance(b.geom, li, last8, ctab);
+    }
+    // After the stream's last literal, by one lane.  The literal lengths have to add up to the stream's literals (a list that ends
+    // early leaves `left` wrapped below zero, one that goes on leaves a Literal command open), and all lengths to its raw size.
+    __device__ __forceinline__ void finish(const LitBatch& b, uint32_t s) {
+        if (!flags) {
+            if (left != 0u) flags = LIT_STATUS_BAD_SEGMENT;
+            else if (pos != rlen) flags = LIT_STATUS_BAD_COMMAND;
+        }
+        if (flags) {
+            if (b.status) atomicOr(b.status, flags);
+            if (b.stream_bad) b.stream_bad[s] = 1;
+        }
+    }
+};
+
 }  // namespace divans_hip
 #endif

@@ -81,9 +81,24 @@ struct LitBatch {
     const uint8_t* byte_rank;
 };
 constexpr uint32_t LIT_DM_PINNED = 1u << 30;
+
+// One command of a general stream as the decoder executes it (divans_lit_command of include/divans_gpu.h): LITERAL decodes `len` bytes
+// under the block type `arg`, COPY repeats `len` bytes from `arg` bytes back, INSERT takes `len` bytes at offset `arg` of the stream's
+// insert bytes (a dictionary word the host has expanded and transformed).  The kinds are the reference's command nibbles.
+struct LitCommand { uint32_t kind, len, arg, reserved; };
+constexpr uint32_t LIT_CMD_COPY = 0u, LIT_CMD_INSERT = 1u, LIT_CMD_LITERAL = 3u;
+// The lists of a batch decoded from its commands (launch_decode2_commands): LitBatch::out / out_offsets / out_sizes are then the
+// streams' RAW ranges and `lit_sizes` their literal bytes; LitBatch::seg_begin / segs stay null
+struct LitCommandLists {
+    const uint32_t* cmd_begin;  // [n_streams + 1] first command of every stream in `cmds`
+    const LitCommand* cmds;
+    const uint32_t* lit_sizes;  // [n_streams] literal bytes the stream's coded bytes hold
+    const uint8_t* ins; const uint64_t* ins_offsets; const uint32_t* ins_sizes;   // insert bytes of every stream, or all null
+};
 constexpr uint32_t LIT_STATUS_BAD_MODEL = 1u;    // rANS pass: freq == 0 or start/freq outside 15 bits
 constexpr uint32_t LIT_STATUS_BAD_SEGMENT = 4u;   // a segment names a literal block type outside the codec's context tables, or a stream's segment lengths do not add up to it
 constexpr uint32_t LIT_STATUS_OUTPUT_FULL = 8u;   // divans_gpu_lit_encode_packed: the coded streams did not fit the caller's buffer
+constexpr uint32_t LIT_STATUS_BAD_COMMAND = 16u;  // decode from commands: a copy from in front of the stream, an insert outside its bytes, an unknown kind, lengths that do not add up to the raw size
 constexpr uint32_t LIT_STATUS_BAD_STREAM = 2u;    // decode: a chunk did not end with both states at 2^31, or the coded words were not consumed exactly
 
 struct RansBatch {
@@ -191,6 +206,11 @@ hipError_t launch_model_encode(const LitBatch& b, bool mix, uint32_t blocks, hip
 hipError_t launch_rans_encode(const RansBatch& b, hipStream_t st);
 hipError_t launch_decode(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st);
 hipError_t launch_decode2(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st);
+// lit_decode2_kernel with the stream's Copy / Insert commands executed on the device (lit_decode2_cmd_kernel_*): b.dm_log2 = what
+// lit_decode2_commands_caches() leaves, the 2-way organisation whatever b.dm_shift says
+hipError_t launch_decode2_commands(const LitBatch& b, const LitCommandLists& cl, bool mix, uint32_t blocks, hipStream_t st);
+void lit_decode2_commands_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);
+uint32_t lit_decode2_commands_caches(uint32_t dm_log2, bool mix, uint32_t total_rows);   // the high-row caches of dm_log2, or none
 void lit_decode_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);    // the instances the two launchers pick, as rocprofv3 spells them
 void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);
 uint32_t lit_decode2_effective_caches(uint32_t dm_log2, bool mix, bool seg);   // the caches of dm_log2 a kernel instance exists for

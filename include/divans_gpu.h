@@ -126,6 +126,42 @@ int divans_gpu_lit_decode_segments_batch(divans_gpu_codec *c, const uint8_t *d_i
                                          const uint32_t *d_seg_begin, const divans_lit_segment *d_segs, uint8_t *d_out,
                                          const uint64_t *d_out_offsets, const uint32_t *d_out_sizes, uint32_t stream_len);
 
+/* ---- general streams decoded from their command lists ---------------------------------------------------------------
+ * What a decompressor has: no plaintext to take divans_lit_segment::last8 from, but the stream's commands.  The decoder runs
+ * them: the stream's output starts empty, a LITERAL command decodes `len` bytes from the LIT coder under the block type `arg`
+ * with the last eight bytes of the output so far as its context (zeros in front of the stream's start), a COPY command appends
+ * out[pos + i] = out[pos + i - distance] byte by byte (an overlapping copy repeats), an INSERT command appends `len` bytes of
+ * the stream's insert bytes -- a dictionary word the host has looked up and transformed.  Commands in front of the first
+ * literal, between literals and behind the last one all run (src/cmd_to_raw/mod.rs:69-86, src/codec/mod.rs:771-783).
+ * Priors, Weights, rANS states, chunks and the integrity check are those of divans_gpu_lit_decode_batch. */
+enum { DIVANS_CMD_COPY = 0, DIVANS_CMD_INSERT = 1, DIVANS_CMD_LITERAL = 3 };   /* the reference's command nibbles */
+typedef struct divans_lit_command {
+    uint32_t kind;
+    uint32_t len;       /* bytes this command adds to the output; 0 is allowed and does nothing */
+    uint32_t arg;       /* LITERAL: literal block type; COPY: distance, 1 .. bytes produced so far by this stream;
+                           INSERT: offset of its bytes inside the stream's insert bytes */
+    uint32_t reserved;  /* 0 */
+} divans_lit_command;
+/* Stream i: coded bytes d_in + d_in_offsets[i] (d_in_sizes[i] of them) holding d_lit_sizes[i] literal bytes (none above
+ * lit_stream_len <= max_stream_len), commands d_cmds[d_cmd_begin[i] .. d_cmd_begin[i+1]), insert bytes d_ins + d_ins_offsets[i]
+ * (d_ins_sizes[i] of them; all three NULL: the batch has no INSERT commands), output d_raw + d_raw_offsets[i] of d_raw_sizes[i]
+ * bytes.  All arrays are device memory.
+ * Every command is checked on the device before it runs, whatever the coded bytes hold: nothing outside a stream's own raw range
+ * is written, nothing outside its raw, insert and coded ranges is read.  DIVANS_GPU_STATUS_BAD_SEGMENT: the LITERAL lengths do
+ * not add up to d_lit_sizes[i], or a block type lies outside the codec's tables.  DIVANS_GPU_STATUS_BAD_COMMAND: a distance of 0
+ * or beyond the bytes produced so far, an insert range outside d_ins_sizes[i], an unknown kind, or lengths that do not add up to
+ * d_raw_sizes[i] (a command of length 0 is skipped unchecked but for its kind).  Both also set the stream's flag
+ * (divans_gpu_codec_set_stream_flags); such a stream's raw range is unspecified afterwards, every other stream is unaffected.
+ * Runs on decoder generations 2 / 3 with the high-row caches (2-way) or, above 32 766 rows per stream, none -- whatever
+ * organisation was asked for; DIVANS_GPU_EINVAL where the codec decodes with generation 1 (speeds whose row totals leave i16)
+ * and while a stream coded call by call is open.  Takes no part in the table-placement search. */
+int divans_gpu_lit_decode_commands_batch(divans_gpu_codec *c,
+        const uint8_t *d_in, const uint64_t *d_in_offsets, const uint32_t *d_in_sizes, uint32_t n_streams,
+        const uint32_t *d_cmd_begin, const divans_lit_command *d_cmds,
+        const uint32_t *d_lit_sizes, uint32_t lit_stream_len,
+        const uint8_t *d_ins, const uint64_t *d_ins_offsets, const uint32_t *d_ins_sizes,
+        uint8_t *d_raw, const uint64_t *d_raw_offsets, const uint32_t *d_raw_sizes);
+
 /* One stream coded piece by piece from host memory, with bounded memory: what the per-stream encoder of include/divans_ffi.h runs
  * for every Literal command the moment the reference would code it (src/divans_compressor.rs:276-337; the LIT coder of
  * src/codec/literal.rs:261-394 with its 65 536-symbol chunks, src/ans.rs:287-378).
@@ -160,6 +196,7 @@ int divans_gpu_lit_stream_decode(divans_gpu_codec *c, const uint8_t *coded, size
 #define DIVANS_GPU_STATUS_BAD_STREAM 2u
 #define DIVANS_GPU_STATUS_BAD_SEGMENT 4u   /* a segment's literal block type lies outside the tables divans_gpu_codec_set_block_types built, or a
                                               stream's segment lengths do not add up to its size */
+#define DIVANS_GPU_STATUS_BAD_COMMAND 16u  /* divans_gpu_lit_decode_commands_batch: a command that cannot run (see there) */
 int divans_gpu_codec_status(divans_gpu_codec *c, uint32_t *status);
 /* Clears the word without waiting (stream-ordered, before the launches that follow): for callers that keep a codec across calls
  * and may have abandoned a launch sequence without reading its status. */

@@ -46,6 +46,14 @@ size_t divans_ir_num_segments(const divans_ir *ir);
 uint32_t divans_ir_num_block_types(const divans_ir *ir);   /* highest literal block type + 1 */
 int divans_ir_literal_segments(const divans_ir *ir, uint8_t *lit, size_t lit_cap, divans_lit_segment *segs, size_t seg_cap);
 
+/* What a decompressor hands the GPU (divans_gpu_lit_decode_commands_batch): the IR's Literal / Copy / Dict commands in order as
+ * divans_lit_command records -- BlockSwitchLiteral folded into every LITERAL's `arg` as it is into a segment's btype, Dict as
+ * INSERT with the word's bytes appended to `ins` and their offset there in `arg` -- host memory, nothing else of the IR.
+ * divans_ir_num_device_commands() records and divans_ir_insert_size() bytes. */
+size_t divans_ir_num_device_commands(const divans_ir *ir);
+size_t divans_ir_insert_size(const divans_ir *ir);
+int divans_ir_device_commands(const divans_ir *ir, divans_lit_command *cmds, size_t cmd_cap, uint8_t *ins, size_t ins_cap);
+
 /* The compressor options that shape the PredictionMode command (DivansCompressorOptions, src/interface.rs:444-484) */
 typedef struct divans_ir_options {
     uint8_t dynamic_context_mixing;   /* default 1 */
