@@ -211,6 +211,8 @@ def load_library():
     L.divans_ir_expand.argtypes = [vp, vp, sz]
     L.divans_ir_literal_segments.argtypes = [vp, vp, sz, vp, sz]
     L.divans_gpu_lit_decode_commands_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.divans_gpu_lit_encode_commands_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp]
+    L.divans_gpu_codec_last_prepare_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.divans_gpu_codec_set_stream_flags.argtypes = [vp, vp]
     for name in ("divans_ir_num_device_commands", "divans_ir_insert_size"):
         getattr(L, name).argtypes = [vp]; getattr(L, name).restype = sz
@@ -242,6 +244,7 @@ def exported_symbols():
         "divans_gpu_codec_set_geometry", "divans_gpu_codec_set_split_cache", "divans_gpu_codec_tune_tables", "divans_gpu_codec_search_tables", "divans_gpu_codec_table_placement", "divans_gpu_table_memory", "divans_gpu_set_table_va_cap", "divans_gpu_trim", "divans_gpu_codec_set_decoder", "divans_gpu_codec_set_high_row_pinning", "divans_gpu_experimental_decoders", "divans_gpu_codec_set_byte_order", "divans_gpu_codec_byte_order", "divans_gpu_codec_row_replay", "divans_gpu_codec_set_rans_split", "divans_gpu_codec_set_encode_path", "divans_gpu_codec_last_encode_path", "divans_gpu_codec_set_bucket_batch", "divans_gpu_codec_high_row_slots", "divans_gpu_codec_bucket_stride", "divans_gpu_lit_model_batch",
         "divans_gpu_selftest_division", "divans_gpu_speed_supported", "divans_gpu_speed_accepted", "divans_gpu_codec_status", "divans_gpu_codec_clear_status", "divans_gpu_codec_status_async", "divans_gpu_codec_last_decode_kernel", "divans_gpu_codec_set_stream_flags", "divans_gpu_codec_set_block_types",
         "divans_gpu_lit_encode_segments_batch", "divans_gpu_lit_decode_segments_batch", "divans_gpu_lit_decode_commands_batch",
+        "divans_gpu_lit_encode_commands_batch", "divans_gpu_codec_last_prepare_ms",
         "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_cdf_ops_on", "divans_gpu_selftest_rans_pairs", "divans_gpu_selftest_rans_batch", "divans_gpu_lit_encode_batch_chunks",
         "divans_gpu_lit_encode_host_pipelined", "divans_gpu_lit_decode_host_pipelined", "divans_gpu_host_alloc", "divans_gpu_host_free",
         "divans_gpu_lit_stream_begin", "divans_gpu_lit_stream_encode", "divans_gpu_lit_stream_finish",
@@ -643,8 +646,26 @@ class LiteralCodec:
             lit_sizes.data_ptr(), int(lit_stream_len), p(ins), p(ins_offsets), p(ins_sizes), d_raw.data_ptr(), raw_offsets.data_ptr(),
             raw_sizes.data_ptr()), "divans_gpu_lit_decode_commands_batch")
 
+    def encode_commands_batch(self, d_raw, raw_offsets, raw_sizes, n_streams, cmd_begin, cmds, lit_stream_len, outputs, lit_sizes,
+                              ins=None, ins_offsets=None, ins_sizes=None):
+        """General streams from their raw bytes and command lists (device tensors as decode_commands_batch takes them; `outputs` as
+        encode_segments_batch): the device derives literals and segments, checks that the Copy / Insert commands reproduce the raw
+        bytes and codes the literals; lit_sizes int32[n] receives every stream's literal bytes, what decode_commands_batch is told."""
+        p = lambda t: t.data_ptr() if t is not None else None
+        _check(self._lib.divans_gpu_lit_encode_commands_batch(
+            self._h, d_raw.data_ptr(), raw_offsets.data_ptr(), raw_sizes.data_ptr(), int(n_streams), cmd_begin.data_ptr(), cmds.data_ptr(),
+            int(lit_stream_len), p(ins), p(ins_offsets), p(ins_sizes), outputs["out"].data_ptr(), int(outputs["slot"]),
+            outputs["offsets"].data_ptr(), outputs["sizes"].data_ptr(), lit_sizes.data_ptr()), "divans_gpu_lit_encode_commands_batch")
+
+    def last_prepare_ms(self):
+        """device time of the prepare kernel inside the last encode_commands_batch call"""
+        ms = ctypes.c_float(0)
+        _check(self._lib.divans_gpu_codec_last_prepare_ms(self._h, ctypes.byref(ms)), "divans_gpu_codec_last_prepare_ms")
+        return ms.value
+
     def set_stream_flags(self, d_flags):
-        """a device uint8 tensor (>= n_streams, zeroed by the caller) that receives a 1 for every stream a decode call reports, or None"""
+        """a device uint8 tensor (>= n_streams, zeroed by the caller) that receives a 1 for every stream a decode call or
+        encode_commands_batch reports, or None"""
         _check(self._lib.divans_gpu_codec_set_stream_flags(self._h, d_flags.data_ptr() if d_flags is not None else None), "divans_gpu_codec_set_stream_flags")
 
     def stream_encode_pieces(self, pieces):

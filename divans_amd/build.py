@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdivans_hip.so")
-SOURCES = ["lit_kernels.hip", "lit_decode2.hip", "lit_bucket.hip", "lit_bucket_mix.hip", "lit_bucket_ctx.hip", "capi.cpp", "host_stream.cpp",
+SOURCES = ["lit_kernels.hip", "lit_decode2.hip", "lit_bucket.hip", "lit_bucket_mix.hip", "lit_bucket_ctx.hip", "lit_commands.hip", "capi.cpp", "host_stream.cpp",
            "ffi.cpp", "ir.cpp", "batch.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # The decoders that lost their measurements (generation 4 = lit_decode_t.hip, generation 1 with unified / split caches; lit_kernels.h)

@@ -182,6 +182,9 @@ struct divans_gpu_codec {
     uint32_t last_encode_path = 0;   // the model pass of the last encode / model call: 1 streaming, 2 bucketed, 3 bucketed two-model (0: none yet)
     uint8_t* d_bk = nullptr;      size_t bk_bytes = 0; uint32_t bk_streams = 0;
     uint8_t* d_rs = nullptr;      size_t rs_bytes = 0;
+    // divans_gpu_lit_encode_commands_batch: what lit_commands_prepare_kernel leaves for the segment encoders (grow-only, one allocation)
+    uint8_t* d_cp = nullptr;      size_t cp_bytes = 0;
+    hipEvent_t ev_cp[2] = {nullptr, nullptr}; float last_prepare_ms = 0; bool timing_pending_cp = false;
     void* host_scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // device buffers of the host-buffer entry points, grow-only
     size_t host_scratch_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // chunk-parallel rANS scratch when the bucket arrays are not there to reuse
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -708,6 +711,8 @@ extern "C" void divans_gpu_codec_destroy(divans_gpu_codec* c) {
     if (c->d_slot_off) (void)hipFree(c->d_slot_off);
     for (hipEvent_t e : c->ev_span) (void)hipEventDestroy(e);
     if (c->d_rs) (void)hipFree(c->d_rs);
+    if (c->d_cp) (void)hipFree(c->d_cp);
+    for (auto& e : c->ev_cp) if (e) (void)hipEventDestroy(e);
     if (c->d_sp) (void)hipFree(c->d_sp);
     if (c->d_wstate) (void)hipFree(c->d_wstate);
     for (void* q : c->host_scratch) if (q) (void)hipFree(q);
@@ -1500,6 +1505,78 @@ extern "C" int divans_gpu_lit_decode_commands_batch(divans_gpu_codec* c, const u
     return 0;
 }
 
+// General streams encoded from their command lists: the kernels of lit_commands.hip derive the literals and the segment
+// list of every stream from its raw bytes and commands and checks that the Copy / Insert commands reproduce the raw bytes; the segment
+// encoders then run on those lists as they do for divans_gpu_lit_encode_segments_batch.  The work arrays are one codec-owned
+// allocation that only grows: round_up(lit_stream_len, 16) + 16 bytes per stream (literal slot, offset, size, segment begin) and 16
+// bytes per command (room for its segment: a stream has one per Literal command with bytes).  Their size needs the number of commands, which only the device knows: the two ends of
+// d_cmd_begin are read back, which waits for the codec's stream once per call.
+extern "C" int divans_gpu_lit_encode_commands_batch(divans_gpu_codec* c, const uint8_t* d_raw, const uint64_t* d_raw_offsets,
+                                                    const uint32_t* d_raw_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                                    const divans_lit_command* d_cmds, uint32_t lit_stream_len,
+                                                    const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                                    uint8_t* d_out, uint64_t out_slot, uint64_t* d_out_offsets, uint32_t* d_out_sizes,
+                                                    uint32_t* d_lit_sizes) {
+    if (!c || !d_raw || !d_raw_offsets || !d_raw_sizes || !d_cmd_begin || !d_cmds || !d_out || !d_out_offsets || !d_out_sizes || !d_lit_sizes)
+        return fail(DIVANS_GPU_EINVAL, "null argument");
+    if ((d_ins == nullptr) != (d_ins_offsets == nullptr) || (d_ins == nullptr) != (d_ins_sizes == nullptr))
+        return fail(DIVANS_GPU_EINVAL, "insert bytes, their offsets and their sizes go together");
+    if (lit_stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "lit_stream_len exceeds the codec's max_stream_len");
+    if (c->sp_started || c->sd_started) return fail(DIVANS_GPU_EINVAL, "a stream coded call by call is open on this codec");
+    if (out_slot % 16 != 0 || out_slot < divans_gpu_lit_encode_bound(c->max_stream_len))      // what encode_batch_impl refuses, before anything is launched
+        return fail(DIVANS_GPU_ECAP, "out_slot must be a multiple of 16 and >= divans_gpu_lit_encode_bound()");
+    if (n_streams == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t ends[2] = {0u, 0u};
+    HIP_TRY(hipMemcpyAsync(&ends[0], d_cmd_begin, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&ends[1], d_cmd_begin + n_streams, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (ends[1] < ends[0]) return fail(DIVANS_GPU_EINVAL, "d_cmd_begin does not ascend");
+    const size_t n = n_streams, n_cmds = ends[1] - ends[0];
+    const uint64_t lit_slot = ((uint64_t)lit_stream_len + 15u) & ~(uint64_t)15u;
+    // [segments: 16 per command, at least one][literal offsets: 8 n, rounded up to 16][literal slots: lit_slot n][literal sizes: 4 n][segment begins: 4 (n + 1)]
+    const size_t sz_segs = std::max<size_t>(n_cmds, 1u) * sizeof(LitSegment), sz_off = (n * sizeof(uint64_t) + 15u) & ~(size_t)15u, sz_lit = n * (size_t)lit_slot;
+    const size_t need = sz_segs + sz_off + sz_lit + n * sizeof(uint32_t) + (n + 1u) * sizeof(uint32_t);
+    if (need > c->cp_bytes) {
+        if (c->d_cp) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_cp)); c->d_cp = nullptr; c->cp_bytes = 0; }
+        if (device_alloc((void**)&c->d_cp, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(work arrays of the command lists) failed");
+        c->cp_bytes = need;
+    }
+    for (auto& e : c->ev_cp) if (!e) HIP_TRY(hipEventCreate(&e));
+    LitCommandPrepare p;
+    std::memset(&p, 0, sizeof(p));
+    p.raw = d_raw; p.raw_offsets = d_raw_offsets; p.raw_sizes = d_raw_sizes;
+    p.n_streams = n_streams; p.lit_stream_len = lit_stream_len;
+    p.cmd_begin = d_cmd_begin; p.cmds = (const LitCommand*)d_cmds; p.cmd_first = ends[0]; p.cmd_last = ends[1];
+    p.ins = d_ins; p.ins_offsets = d_ins_offsets; p.ins_sizes = d_ins_sizes;
+    p.bt_first = c->geom.bt_first; p.n_btypes = c->geom.n_btypes;
+    p.segs = (LitSegment*)c->d_cp;
+    p.lit_offsets = (uint64_t*)(c->d_cp + sz_segs);
+    p.lit = c->d_cp + sz_segs + sz_off; p.lit_slot = lit_slot;
+    p.lit_sizes = (uint32_t*)(p.lit + sz_lit);
+    p.seg_begin = p.lit_sizes + n;
+    p.out_lit_sizes = d_lit_sizes;
+    p.status = c->d_status; p.stream_bad = c->d_stream_flags;
+    HIP_TRY(hipEventRecord(c->ev_cp[0], c->stream));
+    HIP_TRY(launch_commands_prepare(p, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_cp[1], c->stream));
+    c->timing_pending_cp = true;
+    return encode_batch_impl(c, p.lit, p.lit_offsets, p.lit_sizes, lit_stream_len, n_streams, d_out, out_slot, d_out_offsets, d_out_sizes,
+                             nullptr, 0, p.seg_begin, (const divans_lit_segment*)p.segs);
+}
+
+extern "C" int divans_gpu_codec_last_prepare_ms(divans_gpu_codec* c, float* ms) {
+    if (!c || !ms) return fail(DIVANS_GPU_EINVAL, "null argument");
+    if (c->timing_pending_cp) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipEventSynchronize(c->ev_cp[1]));
+        HIP_TRY(hipEventElapsedTime(&c->last_prepare_ms, c->ev_cp[0], c->ev_cp[1]));
+        c->timing_pending_cp = false;
+    }
+    *ms = c->last_prepare_ms;
+    return 0;
+}
+
 // Cache organisation and grid of lit_decode2_kernel for a batch of n_streams (also what divans_gpu_codec_row_replay launches with)
 static void decode2_shape(divans_gpu_codec* c, uint32_t n_streams, bool segs, LitBatch& b, uint32_t& grid) {
     b.dm_log2 = lit_decode2_effective_caches(c->dm_log2, c->mix, segs); b.dm_shift = c->dm_shift;
@@ -1767,7 +1844,7 @@ extern "C" int divans_gpu_codec_info(divans_gpu_codec* c, divans_gpu_info* info)
     info->resident_groups = resident_groups(c);
     info->blocks = c->blocks; info->threads = LIT_THREADS;
     info->table_bytes = (uint64_t)resident_groups(c) * c->geom.total_rows * 32u;
-    info->scratch_bytes = c->sf_bytes + c->bk_bytes + c->rs_bytes + c->slots_bytes;
+    info->scratch_bytes = c->sf_bytes + c->bk_bytes + c->rs_bytes + c->slots_bytes + c->cp_bytes;
     info->last_pack_ms = c->last_pack_ms;
     info->last_model_ms = c->last_model_ms; info->last_rans_ms = c->last_rans_ms; info->last_decode_ms = c->last_decode_ms;
     return 0;

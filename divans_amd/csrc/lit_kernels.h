@@ -95,6 +95,29 @@ struct LitCommandLists {
     const uint32_t* lit_sizes;  // [n_streams] literal bytes the stream's coded bytes hold
     const uint8_t* ins; const uint64_t* ins_offsets; const uint32_t* ins_sizes;   // insert bytes of every stream, or all null
 };
+// The step in front of the segment encoders for a batch ENCODED from its commands (lit_commands.hip, launch_commands_prepare): stream
+// s = raw + raw_offsets[s], raw_sizes[s] bytes at any alignment, commands cmds[cmd_begin[s] .. cmd_begin[s + 1]), insert bytes as in
+// LitCommandLists.  The kernel checks every command, compares what the COPY and INSERT commands would produce with the raw bytes, and
+// leaves what divans_gpu_lit_encode_segments_batch takes: the literals of stream s at lit + s * lit_slot (lit_offsets[s], lit_sizes[s]),
+// its segments at segs[seg_begin[s] .. seg_begin[s + 1]), one per Literal command with bytes (a count kernel and a one-workgroup scan
+// fill seg_begin first).  A stream whose list cannot run or does not reproduce the raw bytes raises LIT_STATUS_BAD_COMMAND /
+// LIT_STATUS_BAD_SEGMENT, sets stream_bad[s] and is left as a stream without literals: empty segments only, lit_sizes[s] = 0.
+struct LitCommandPrepare {
+    const uint8_t* raw; const uint64_t* raw_offsets; const uint32_t* raw_sizes;
+    uint32_t n_streams, lit_stream_len;
+    const uint32_t* cmd_begin; const LitCommand* cmds;
+    uint32_t cmd_first, cmd_last;   // cmd_begin[0], cmd_begin[n_streams] as the host read them: segs holds cmd_last - cmd_first records
+    const uint8_t* ins; const uint64_t* ins_offsets; const uint32_t* ins_sizes;   // or all null
+    uint32_t bt_first, n_btypes;    // the block types a Literal command may name (LitGeometry)
+    uint8_t* lit; uint64_t lit_slot;   // literal slots: lit_stream_len rounded up to 16 bytes each
+    uint64_t* lit_offsets; uint32_t* lit_sizes;   // [n_streams]
+    uint32_t* seg_begin;            // [n_streams + 1]
+    LitSegment* segs;
+    uint32_t* out_lit_sizes;        // [n_streams] the caller's copy of lit_sizes
+    uint32_t* status; uint8_t* stream_bad;
+};
+hipError_t launch_commands_prepare(const LitCommandPrepare& b, hipStream_t st);   // count, scan, prepare: three launches
+
 constexpr uint32_t LIT_STATUS_BAD_MODEL = 1u;    // rANS pass: freq == 0 or start/freq outside 15 bits
 constexpr uint32_t LIT_STATUS_BAD_SEGMENT = 4u;   // a segment names a literal block type outside the codec's context tables, or a stream's segment lengths do not add up to it
 constexpr uint32_t LIT_STATUS_OUTPUT_FULL = 8u;   // divans_gpu_lit_encode_packed: the coded streams did not fit the caller's buffer

@@ -162,6 +162,42 @@ int divans_gpu_lit_decode_commands_batch(divans_gpu_codec *c,
         const uint8_t *d_ins, const uint64_t *d_ins_offsets, const uint32_t *d_ins_sizes,
         uint8_t *d_raw, const uint64_t *d_raw_offsets, const uint32_t *d_raw_sizes);
 
+/* ---- general streams encoded from their command lists ---------------------------------------------------------------
+ * The other direction, with the same inputs: what a compressor has is the raw bytes and the LITERAL / COPY / INSERT list its match
+ * finder wrote, not the literal bytes in command order and a divans_lit_segment per Literal command.  The device derives those
+ * (lit_commands.hip: raw position, literal position and segment index of a command are prefix sums over the list; last8 = the eight
+ * raw bytes in front of a Literal command), VERIFIES that the list describes the raw bytes, and runs the segment encoders on the result:
+ * the coded bytes are those divans_gpu_lit_encode_segments_batch writes for the stream's literals and segments.
+ *   Status 0 means: divans_gpu_lit_decode_commands_batch, given the same lists, these coded bytes and d_lit_sizes, gives the raw
+ *   bytes back.
+ * Stream i: raw bytes d_raw + d_raw_offsets[i] (d_raw_sizes[i] of them, any alignment), commands and insert bytes as above (kinds,
+ * fields, len == 0; all three insert pointers NULL: the batch has no INSERT commands).  d_raw, d_cmds and d_ins are only read.
+ * Output slots, out_slot, d_out_offsets and d_out_sizes as divans_gpu_lit_encode_segments_batch with per-stream sizes (out_slot >=
+ * divans_gpu_lit_encode_bound(max_stream_len), else DIVANS_GPU_ECAP); d_lit_sizes[i] receives the stream's literal bytes (none above
+ * lit_stream_len <= max_stream_len), what the decode call is told.  The encode path (divans_gpu_codec_set_encode_path) applies as
+ * it does to a segment list: streaming kernels by default, the bucketed passes under path 2.
+ * Every command is checked before a byte of it is read: nothing outside a stream's own raw, insert and command ranges is read, nothing
+ * outside the codec's work arrays and the output slots is written.  The first command of a list that fails decides the bit --
+ * DIVANS_GPU_STATUS_BAD_COMMAND: an unknown kind, a distance of 0 or beyond the bytes produced so far, an insert range outside
+ * d_ins_sizes[i], lengths that do not add up to d_raw_sizes[i] (lengths up to 0xffffffff wrap nothing: 64-bit sums), and -- what only
+ * this direction can see -- a COPY whose bytes differ from raw[p - distance] or an INSERT whose bytes differ from the raw bytes at its
+ * place.  DIVANS_GPU_STATUS_BAD_SEGMENT: a literal block type outside the codec's tables, or LITERAL lengths that add up to more than
+ * lit_stream_len.  Such a stream also sets its flag (divans_gpu_codec_set_stream_flags), gets d_lit_sizes[i] = 0 and is coded as a
+ * stream without literals; every other stream is unaffected.
+ * Work memory, codec-owned, grow-only, released by divans_gpu_codec_destroy: round_up(lit_stream_len, 16) + 16 bytes per stream
+ * (literal slot, offset, size, segment begin) and 16 bytes per command (room for one segment record each; a stream gets one per LITERAL
+ * command with bytes).  Sizing it takes the two ends of d_cmd_begin, which are read back: the call waits for the codec's stream
+ * once before it launches.  DIVANS_GPU_EINVAL for null arguments, an incomplete insert triple, lit_stream_len > max_stream_len,
+ * a d_cmd_begin whose last entry lies below its first, and while a stream coded call by call is open. */
+int divans_gpu_lit_encode_commands_batch(divans_gpu_codec *c,
+        const uint8_t *d_raw, const uint64_t *d_raw_offsets, const uint32_t *d_raw_sizes, uint32_t n_streams,
+        const uint32_t *d_cmd_begin, const divans_lit_command *d_cmds, uint32_t lit_stream_len,
+        const uint8_t *d_ins, const uint64_t *d_ins_offsets, const uint32_t *d_ins_sizes,
+        uint8_t *d_out, uint64_t out_slot, uint64_t *d_out_offsets, uint32_t *d_out_sizes,
+        uint32_t *d_lit_sizes /* out: literal bytes of stream i, what the decode call is told */);
+/* hipEvent time of the prepare step (three small launches: count, scan, prepare) inside the last divans_gpu_lit_encode_commands_batch call (0 before the first); waits for it. */
+int divans_gpu_codec_last_prepare_ms(divans_gpu_codec *c, float *ms);
+
 /* One stream coded piece by piece from host memory, with bounded memory: what the per-stream encoder of include/divans_ffi.h runs
  * for every Literal command the moment the reference would code it (src/divans_compressor.rs:276-337; the LIT coder of
  * src/codec/literal.rs:261-394 with its 65 536-symbol chunks, src/ans.rs:287-378).
@@ -196,7 +232,8 @@ int divans_gpu_lit_stream_decode(divans_gpu_codec *c, const uint8_t *coded, size
 #define DIVANS_GPU_STATUS_BAD_STREAM 2u
 #define DIVANS_GPU_STATUS_BAD_SEGMENT 4u   /* a segment's literal block type lies outside the tables divans_gpu_codec_set_block_types built, or a
                                               stream's segment lengths do not add up to its size */
-#define DIVANS_GPU_STATUS_BAD_COMMAND 16u  /* divans_gpu_lit_decode_commands_batch: a command that cannot run (see there) */
+#define DIVANS_GPU_STATUS_BAD_COMMAND 16u  /* divans_gpu_lit_decode_commands_batch: a command that cannot run (see there);
+                                              divans_gpu_lit_encode_commands_batch: that, or one that does not reproduce the raw bytes */
 int divans_gpu_codec_status(divans_gpu_codec *c, uint32_t *status);
 /* Clears the word without waiting (stream-ordered, before the launches that follow): for callers that keep a codec across calls
  * and may have abandoned a launch sequence without reading its status. */
@@ -206,7 +243,8 @@ int divans_gpu_codec_clear_status(divans_gpu_codec *c);
  * costs ~10 ms per call while other streams keep the device busy.) */
 int divans_gpu_codec_status_async(divans_gpu_codec *c, uint32_t *h_pinned_status);
 /* Which stream: `d_flags` (device memory, >= n_streams bytes, zeroed by the caller; NULL = off) receives a 1 for every stream
- * of the following decode calls that fails that integrity check. */
+ * of the following decode calls that fails that integrity check, and for every stream of a divans_gpu_lit_encode_commands_batch
+ * call whose command list cannot run or does not reproduce its raw bytes. */
 int divans_gpu_codec_set_stream_flags(divans_gpu_codec *c, uint8_t *d_flags);
 
 /* Compacts the right-aligned slots into one contiguous buffer (4-byte aligned starts):
