@@ -113,6 +113,40 @@ static void make_luts(uint8_t mode, uint8_t* lut0, uint8_t* lut1) {
 // the CDF tables' memory: a hipMalloc block (chunks empty) or an address range with physical chunks mapped into it (table_alloc)
 struct TableMem { int16_t* p = nullptr; size_t bytes = 0; std::vector<hipMemGenericAllocationHandle_t> chunks; size_t chunk_bytes = 0, va_bytes = 0; int device = 0; };
 
+// The bucketed encoder model passes.  A configuration is covered by at most one of them (configure_from_geometry).
+enum BucketPass : uint32_t {
+    PASS_NONE,      // streaming kernels only
+    PASS_STRIDE,    // one model, mixing value 4 with the context a function of the previous byte, or strides 2 / 3 / 4 / 8 under a constant context: lit_bucket.hip
+    PASS_MIX,       // two models, mixing value 4, one block type: lit_bucket_mix.hip
+    PASS_CTX,       // context-keyed rows (every mixing value 0), one model: lit_bucket_ctx.hip
+    PASS_CTX_MIX,   //   ... two models
+    PASS_MIX_BT,    // two models, mixing value 4, several block types, at most 8 high rows per previous byte (mix_bt_sort_kernel)
+};
+// two_models: the MixBucketBatch work arrays (ensure_bucket_mix) and last_encode_path 3, else the BucketBatch layout and 2.
+// task_ids: task ids are stream * 256 + key in 32 bits, so the pass takes calls of fewer than 2^24 streams only.
+struct PassTraits { bool two_models, task_ids; };
+constexpr PassTraits kPassTraits[] = {
+    /* PASS_NONE */ {false, false}, /* PASS_STRIDE */ {false, true}, /* PASS_MIX */ {true, false},
+    /* PASS_CTX */ {false, true},   /* PASS_CTX_MIX */ {true, true}, /* PASS_MIX_BT */ {true, true},
+};
+
+// The device buffers of the host-buffer entry points, one name per role.  Roles that share a number share a buffer: no entry point uses both.
+enum HostBuf {
+    HB_IN = 0,              // the call's input bytes
+    HB_SLOTS = 1,           // encode: right-aligned output slots
+    HB_DECODED = 1,         // decode: the literal bytes
+    HB_PACKED = 2,          // encode: the packed streams
+    HB_OFFSETS = 3,         // encode: slot offsets; decode: the coded streams' offsets
+    HB_PACKED_OFFSETS = 4,  // encode: offsets into the packed bytes
+    HB_CHUNK_SLOTS = 4,     // piece by piece: output slots of the complete chunks
+    HB_TOTALS = 5,          // encode: packed bytes per call / per slice
+    HB_CHUNK_OFFSETS = 5,   // piece by piece: slot offsets of the complete chunks
+    HB_SIZES = 6,           // coded sizes (piece by piece: and the chunks' lengths behind them)
+    HB_CHUNK_BYTES = 7,     // encode: coded bytes of every 65 536-symbol chunk
+    HB_META = 7,            // piece by piece: segment list (and offset / size / consumed words) of the one stream
+    HB_COUNT = 8
+};
+
 struct divans_gpu_codec {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -165,28 +199,24 @@ struct divans_gpu_codec {
     uint64_t table_launch_seq = 0;                  // launches that read or write the CDF tables (may a placement be freed without a stream sync?)
     uint32_t* d_sf = nullptr;     size_t sf_bytes = 0;
     uint32_t* d_status = nullptr;
-    // bucketed encoder model pass (lit_bucket.hip)
-    bool bucket_ok = false;       // the configuration allows it: order-1 rows (see configure_from_geometry), no mixing, streams <= 64 KiB
+    BucketPass bucket_pass = PASS_NONE;   // the bucketed encoder model pass that covers this configuration (configure_from_geometry)
     uint32_t stride_dist = 0;     // the stride distance every reachable mixing value selects (derive_stride_distance), 0: none / not one
-    uint32_t bucket_stride = 0;   // bucket_ok: the distance its buckets are keyed by -- 1, or 2 / 3 / 4 / 8 (bucket_sort_stride_kernel); else 0
-    bool bucket_mix_ok = false;   // two-model configuration the bucketed pass of lit_bucket_mix.hip covers
-    bool bucket_ctx_ok = false, bucket_ctx_mix_ok = false;   // context-keyed rows (every mixing value 0), one model / two: lit_bucket_ctx.hip
-    bool bucket_mix_bt_ok = false;   // two models, mixing value 4, several block types, at most 8 high rows per previous byte (mix_bt_sort_kernel)
+    uint32_t bucket_stride = 0;   // PASS_STRIDE: the distance its buckets are keyed by -- 1, or 2 / 3 / 4 / 8 (bucket_sort_stride_kernel); else 0
     uint32_t high_row_slots = 0;     // the most distinct contexts one previous byte reaches over the codec's block types (derive_high_row_slots)
     uint32_t bucket_mix_batch = 32768;   // streams per launch sequence of the bucketed passes (work arrays are sized for this many)
     uint8_t* d_slots = nullptr; size_t slots_bytes = 0;      // divans_gpu_lit_encode_packed: right-aligned output slots of ONE sub-batch
-    uint64_t* d_slot_off = nullptr; size_t slot_off_cap = 0;
+    uint64_t* d_slot_off = nullptr; size_t slot_off_bytes = 0;
     std::vector<hipEvent_t> ev_span; size_t enc_spans = 0;   // ... and its events: per sub-batch (start, before the pack, end)
     float last_pack_ms = 0;
-    uint32_t encode_path = 0;     // 0 automatic (bucketed when bucket_ok -- stride 1, or 2 / 3 / 4 / 8 under a constant context -- / bucket_mix_ok / bucket_ctx*_ok / bucket_mix_bt_ok and the call has no segment list), 1 streaming kernels, 2 bucketed
+    uint32_t encode_path = 0;     // divans_gpu_codec_set_encode_path: 0 automatic, 1 streaming kernels, 2 bucketed (select_pass)
     uint32_t last_encode_path = 0;   // the model pass of the last encode / model call: 1 streaming, 2 bucketed, 3 bucketed two-model (0: none yet)
-    uint8_t* d_bk = nullptr;      size_t bk_bytes = 0; uint32_t bk_streams = 0;
+    uint8_t* d_bk = nullptr;      size_t bk_bytes = 0;
     uint8_t* d_rs = nullptr;      size_t rs_bytes = 0;
     // divans_gpu_lit_encode_commands_batch: what lit_commands_prepare_kernel leaves for the segment encoders (grow-only, one allocation)
     uint8_t* d_cp = nullptr;      size_t cp_bytes = 0;
     hipEvent_t ev_cp[2] = {nullptr, nullptr}; float last_prepare_ms = 0; bool timing_pending_cp = false;
-    void* host_scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // device buffers of the host-buffer entry points, grow-only
-    size_t host_scratch_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // chunk-parallel rANS scratch when the bucket arrays are not there to reuse
+    void* host_scratch[HB_COUNT] = {};         // device buffers of the host-buffer entry points (HostBuf), grow-only
+    size_t host_scratch_cap[HB_COUNT] = {};
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     // pipelined host-buffer entry points: copy-in / copy-out streams, per-slice events, pinned per-slice totals
     hipStream_t s_in = nullptr, s_out = nullptr;
@@ -402,6 +432,19 @@ static void set_cache_fields(const divans_gpu_codec* c, LitBatch& b) {
     b.cache_bytes_per_wg = (LIT_THREADS / 16) * (b.cache_rows_high + b.cache_rows_low) * 34u;
 }
 
+// A zeroed LitBatch with what every launch on the codec's tables has in common (callers have run ensure_tables); the streams' input
+// and output, segment lists and caches are the caller's.
+static LitBatch lit_batch(const divans_gpu_codec* c, uint32_t n_streams, uint32_t stream_len) {
+    LitBatch b;
+    std::memset(&b, 0, sizeof(b));
+    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
+    b.n_streams = n_streams; b.stream_len = stream_len; b.max_stream_len = c->max_stream_len;
+    b.status = c->d_status;
+    return b;
+}
+// LitBatch::byte_rank of the decode launches: the learned or hinted order once it is on the device, null = numeric
+static const uint8_t* byte_rank_of(const divans_gpu_codec* c) { return (c->byte_order != 1u && c->rank_ready) ? c->d_rank : nullptr; }
+
 static uint32_t groups_per_block(const divans_gpu_codec*) { return LIT_THREADS / 16; }
 static bool use_decode2(const divans_gpu_codec* c) { return c->decode_gen == 2u && c->blocks2 != 0u && !c->geom.wrap_check; }
 #if DIVANS_WITH_EXPERIMENTAL_DECODERS
@@ -592,13 +635,26 @@ static int ensure_tables(divans_gpu_codec* c) {
     return 0;
 }
 
-static int ensure_sf(divans_gpu_codec* c, uint32_t n_streams) {
-    const size_t need = (size_t)n_streams * 2u * c->max_stream_len * sizeof(uint32_t);
-    if (need <= c->sf_bytes) return 0;
-    if (c->d_sf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_sf)); c->d_sf = nullptr; c->sf_bytes = 0; }
-    if (device_alloc((void**)&c->d_sf, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(start/freq spill) failed");
-    c->sf_bytes = need;
+// The codec's work buffers only grow.  One that is too small is freed once the stream has finished with it and allocated anew
+// (device_alloc: the idle table ranges go first when memory is short); `oom` is the message of the call that fails then.
+template <typename T>
+static int grow_buffer(divans_gpu_codec* c, T*& p, size_t& cap, size_t need, const char* oom) {
+    if (need <= cap) return 0;
+    if (p) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(p)); p = nullptr; cap = 0; }
+    if (device_alloc((void**)&p, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, oom);
+    cap = need;
     return 0;
+}
+
+static int ensure_sf(divans_gpu_codec* c, uint32_t n_streams) {
+    return grow_buffer(c, c->d_sf, c->sf_bytes, (size_t)n_streams * 2u * c->max_stream_len * sizeof(uint32_t), "hipMalloc(start/freq spill) failed");
+}
+
+// LDS a workgroup of the model / decode kernels spends next to its row caches: the context tables unless the context is constant, and
+// the mixing mask unless the mixing value is one the kernels are specialised for (0 or 4, see effective_mm)
+static uint32_t config_lds_bytes(const LitGeometry& g) {
+    const bool mask_in_lds = !(g.mm_uniform == 0 || g.mm_uniform == 4);
+    return (g.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * g.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
 }
 
 // launch geometry, LDS cache organisation and encoder path that follow from the table geometry
@@ -609,12 +665,9 @@ static void configure_from_geometry(divans_gpu_codec* c) {
     if (c->geom.total_rows < 0x7fffu) {
         // the kernels gain more from a seventh wave per SIMD than from the second half of the row cache (DESIGN.md
         // section 7; the non-mixing decode kernel needs 62 VGPRs): 7 workgroups per CU with 32-row caches, fewer when
-        // the context tables of a generic configuration take more of the CU's 160 KB of LDS (the kernels stage the
-        // mixing mask unless the mixing value is one they are specialised for: 0 or 4, see effective_mm)
+        // the context tables of a generic configuration take more of the CU's 160 KB of LDS (config_lds_bytes)
         c->cache_high = 32u;
-        const bool mask_in_lds = !(c->geom.mm_uniform == 0 || c->geom.mm_uniform == 4);
-        const uint32_t lds_per_wg = (LIT_THREADS / 16) * c->cache_high * 34u +
-                                    (c->geom.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * c->geom.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
+        const uint32_t lds_per_wg = (LIT_THREADS / 16) * c->cache_high * 34u + config_lds_bytes(c->geom);
         const uint32_t fit = (160u * 1024u) / lds_per_wg;
         c->blocks = c->num_cus * std::max(1u, std::min(7u, fit));
     }
@@ -631,35 +684,33 @@ static void configure_from_geometry(divans_gpu_codec* c) {
     // placed alike (profiles/r04e_table_placement.txt: 433-442 vs 467-480 ms for 65 536 streams)
     if (!c->mix) c->dm_shift |= 0x80000000u;
     {
-        const bool mask_in_lds = !(c->geom.mm_uniform == 0 || c->geom.mm_uniform == 4);
-        const uint32_t lds_per_wg = (LIT_THREADS / 16) * lit_decode2_stream_lds(c->dm_log2) + 256u /* byte ranks */ +
-                                    (c->geom.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * c->geom.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
+        const uint32_t lds_per_wg = (LIT_THREADS / 16) * lit_decode2_stream_lds(c->dm_log2) + 256u /* byte ranks */ + config_lds_bytes(c->geom);
         const uint32_t fit = (160u * 1024u) / lds_per_wg;
         c->blocks2 = c->num_cus * std::max(1u, std::min(7u, fit));
     }
+    // The bucketed encoder pass of the configuration: streams of at most 64 KiB and one of the five conditions below, of which no two
+    // hold at once (one model or two; mixing value 4, 0 or a stride of 2 and more; one block type or several).  Only the first and the
+    // third take speeds whose row totals leave i16 (wrap_check): select_pass keeps their calls on the streaming kernels then
+    c->bucket_pass = PASS_NONE; c->bucket_stride = 0u;
+    if (c->max_stream_len > 65536u) return;
+    const bool wrap = c->geom.wrap_check != 0;
     // order-1 rows: high row [ctx][prev], low row [prev][hi] with the context constant, or a function of prev alone (one lut1
     // class and one block type: LSB6 / MSB6 -- what the reference's literal-only compressor emits, raw_to_cmd/mod.rs:115-140)
     const bool ctx_from_prev = c->geom.ctx_const >= 0 || (c->geom.lut1_classes == 1u && c->geom.n_btypes == 1u);
-    c->bucket_ok = !c->mix && c->geom.mm_uniform == 4 && ctx_from_prev && c->max_stream_len <= 65536u;
-    c->bucket_stride = c->bucket_ok ? 1u : 0u;
+    if (!c->mix && c->geom.mm_uniform == 4 && ctx_from_prev) { c->bucket_pass = PASS_STRIDE; c->bucket_stride = 1u; }
     // strides 2, 3, 4 and 8 (mixing values 5, 6, 7, and 8 and above): high row [ctx][b_d], low row [b_d][hi] with b_d the byte d places
     // back -- under a CONSTANT context a function of b_d alone, the bucket key (bucket_sort_stride_kernel).  A context that follows
     // from prev (LSB6 / MSB6) would need two key bytes, prev and b_d, and stays on the streaming kernel
-    if (!c->mix && c->stride_dist > 1u && c->geom.ctx_const >= 0 && c->max_stream_len <= 65536u && !c->geom.wrap_check) {
-        c->bucket_ok = true; c->bucket_stride = c->stride_dist;
-    }
+    if (!c->mix && c->stride_dist > 1u && c->geom.ctx_const >= 0 && !wrap) { c->bucket_pass = PASS_STRIDE; c->bucket_stride = c->stride_dist; }
     // both models' rows depend on (prev, ctx, high nibble) only when every mixing value is 4 (stride 1, literal.rs:184-192)
-    c->bucket_mix_ok = c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes == 1u && c->max_stream_len <= 65536u;
+    if (c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes == 1u) c->bucket_pass = PASS_MIX;
     // every mixing value 0: all rows of a position -- of both models -- are a function of its context (literal.rs:176-208), whatever
     // the block types; a constant context would be one bucket per stream and keeps the streaming kernel
-    const bool ctx_keyed = c->geom.mm_uniform == 0 && c->geom.ctx_const < 0 && c->max_stream_len <= 65536u && !c->geom.wrap_check;
-    c->bucket_ctx_ok = !c->mix && ctx_keyed;
-    c->bucket_ctx_mix_ok = c->mix && ctx_keyed;
+    if (c->geom.mm_uniform == 0 && c->geom.ctx_const < 0 && !wrap) c->bucket_pass = c->mix ? PASS_CTX_MIX : PASS_CTX;
     // mixing value 4, two models, several block types: the stride rows stay keyed by prev and the block type enters the high-row slot
     // (derive_high_row_slots); the chain keeps eight high rows per bucket.  A constant context is one bucket per stream for the
     // context model, as above
-    c->bucket_mix_bt_ok = c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes > 1u && c->geom.ctx_const < 0 && c->high_row_slots <= 8u &&
-                          c->max_stream_len <= 65536u && !c->geom.wrap_check;
+    if (c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes > 1u && c->geom.ctx_const < 0 && c->high_row_slots <= 8u && !wrap) c->bucket_pass = PASS_MIX_BT;
 }
 
 extern "C" void divans_gpu_codec_destroy(divans_gpu_codec* c);
@@ -735,36 +786,26 @@ static uint32_t bucket_pieces(const divans_gpu_codec* c) { return (c->max_stream
 // the power-of-two stride changes nothing (profiles/r02c), so it stays 0.
 constexpr uint32_t BUCKET_SLOT_PAD = 0;
 static uint32_t bucket_slot(const divans_gpu_codec* c) { return bucket_pieces(c) * 8192u + BUCKET_SLOT_PAD; }
-static bool use_bucket_mix(const divans_gpu_codec* c) { return c->bucket_mix_ok && c->encode_path != 1u && !c->geom.wrap_check; }
-// the context-keyed passes: on request, and what "automatic" picks for calls without a segment list (the rule the mixing-value-4 passes have:
-// ahead of the streaming kernels at 16 384 and at 64 streams); the flags already exclude wrap_check
-static bool use_bucket_ctx(const divans_gpu_codec* c, bool has_segs) {
-    return (c->bucket_ctx_ok || c->bucket_ctx_mix_ok) && (c->encode_path == 2u || (c->encode_path == 0u && !has_segs));
+// The model pass of one call: the codec's bucketed pass, or PASS_NONE = the streaming kernels.  One rule for every pass: bucketed on
+// request (encode path 2), and what "automatic" (0) picks for calls without a segment list -- there every pass is ahead of the
+// streaming kernels at 16 384 and at 64 streams alike (strides 2 / 3 / 4 / 8: 16 against 95 ms, 5 against 50 ms; DESIGN.md section 7,
+// rounds 8 to 12).  Segment lists (context reloads between Literal commands) go through the streaming kernels unless the caller asked
+// for the bucketed pass: its sort kernels then take the keys of a segment's first bytes from last8.  A wrap-checked speed always runs
+// on the streaming kernels, which report a wrapped row -- also for a codec whose encode path 2 was accepted because its pass exists
+// (divans_gpu_codec_set_encode_path asks only that) -- and so does a call with more streams than the pass's task ids can name.
+static BucketPass select_pass(const divans_gpu_codec* c, bool has_segs, uint32_t n_streams) {
+    if (c->bucket_pass == PASS_NONE || c->geom.wrap_check) return PASS_NONE;
+    if (!(c->encode_path == 2u || (c->encode_path == 0u && !has_segs))) return PASS_NONE;
+    if (kPassTraits[c->bucket_pass].task_ids && n_streams >= (1u << 24)) return PASS_NONE;
+    return c->bucket_pass;
 }
-// mixing value 4, two models, several block types (launch_bucket_mix_bt_model): on request, and what "automatic" picks for calls without
-// a segment list (ahead of the streaming kernels at 16 384 and at 64 streams)
-static bool use_bucket_mix_bt(const divans_gpu_codec* c, bool has_segs) {
-    return c->bucket_mix_bt_ok && (c->encode_path == 2u || (c->encode_path == 0u && !has_segs));
-}
-// The strides 2, 3, 4 and 8 (bucket_stride > 1) included: "automatic" takes the bucketed pass for their calls without a segment list by the
-// rule of the other passes -- ahead of the streaming kernels at 16 384 and at 64 streams (16 against 95 ms, 5 against 50 ms: DESIGN.md section 7, round 12)
-static bool use_bucket(const divans_gpu_codec* c) { return c->bucket_ok && c->encode_path != 1u && !c->geom.wrap_check; }   // task ids are stream * 256 + byte in 32 bits: callers keep n_streams < 2^24
 
 // The bucketed passes' work arrays are one allocation (c->d_bk) that only grows; each pass carves it in its own order.
-static int ensure_bucket_bytes(divans_gpu_codec* c, size_t need, const char* oom) {
-    if (need > c->bk_bytes) {
-        if (c->d_bk) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_bk)); c->d_bk = nullptr; c->bk_bytes = 0; }
-        if (device_alloc((void**)&c->d_bk, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, oom);
-        c->bk_bytes = need;
-    }
-    return 0;
-}
-
 static int ensure_bucket(divans_gpu_codec* c, uint32_t n_streams, BucketBatch& b) {
     const size_t pl = bucket_slot(c);
     const size_t n = n_streams;
     const size_t sz_sfs = n * pl * 8u, sz_desc = n * 256u * 8u * 4u, sz_tasks = n * 256u * 6u * 4u, sz_inv = n * pl * 2u, sz_sorted = n * pl;
-    if (int rc = ensure_bucket_bytes(c, sz_sfs + sz_desc + sz_tasks + sz_inv + sz_sorted + 256u, "hipMalloc(bucketed encoder work arrays) failed")) return rc;
+    if (int rc = grow_buffer(c, c->d_bk, c->bk_bytes, sz_sfs + sz_desc + sz_tasks + sz_inv + sz_sorted + 256u, "hipMalloc(bucketed encoder work arrays) failed")) return rc;
     uint8_t* p = c->d_bk;
     b.counters = (uint32_t*)p; p += 256;
     b.sfs = (bk_u32x2*)p; p += sz_sfs;
@@ -779,7 +820,7 @@ static int ensure_bucket_mix(divans_gpu_codec* c, uint32_t n_streams, MixBucketB
     const size_t pl = bucket_slot(c);
     const size_t n = n_streams;
     const size_t sz_xs = n * pl * 8u, sz_max = n * pl * 4u, sz_desc = n * 256u * 8u * 4u, sz_tasks = n * 256u * 6u * 4u, sz_inv = n * pl * 2u, sz_sorted = n * pl * 2u;
-    if (int rc = ensure_bucket_bytes(c, 256u + 2u * (sz_xs + sz_max) + sz_desc + sz_tasks + sz_inv + sz_sorted, "hipMalloc(bucketed two-model encoder work arrays) failed")) return rc;
+    if (int rc = grow_buffer(c, c->d_bk, c->bk_bytes, 256u + 2u * (sz_xs + sz_max) + sz_desc + sz_tasks + sz_inv + sz_sorted, "hipMalloc(bucketed two-model encoder work arrays) failed")) return rc;
     uint8_t* p = c->d_bk;
     b.counters = (uint32_t*)p; p += 256;
     for (int i = 0; i < 2; ++i) { b.xs[i] = (bk_u32x2*)p; p += sz_xs; }      // 12 bytes per position and model: the entries, then the row totals
@@ -802,11 +843,7 @@ static int ensure_rans_scratch(divans_gpu_codec* c, uint32_t n_streams, const Sf
     const size_t need = (size_t)n_streams * stride + (size_t)n_streams * 4u + 64u;
     uint8_t* base = v.spare_bytes >= need ? v.spare : nullptr;
     if (!base) {
-        if (need > c->rs_bytes) {
-            if (c->d_rs) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_rs)); c->d_rs = nullptr; c->rs_bytes = 0; }
-            if (device_alloc((void**)&c->d_rs, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(rANS chunk scratch) failed");
-            c->rs_bytes = need;
-        }
+        if (int rc = grow_buffer(c, c->d_rs, c->rs_bytes, need, "hipMalloc(rANS chunk scratch) failed")) return rc;
         base = c->d_rs;
     }
     r.chunk0_sizes = (uint32_t*)base;
@@ -836,8 +873,7 @@ extern "C" int divans_gpu_codec_set_block_types(divans_gpu_codec* c, uint32_t n_
         const uint32_t fit_blocks = c->blocks, fit_blocks2 = c->blocks2;
         if (c->geom.total_rows < 0x7fffu) {
             c->cache_high = ch; c->cache_low = cl; c->cache_unified = uni; c->dm_log2 = lg; c->dm_shift = sh;
-            const bool mask_in_lds = !(c->geom.mm_uniform == 0 || c->geom.mm_uniform == 4);
-            const uint32_t extra = (c->geom.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * c->geom.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
+            const uint32_t extra = config_lds_bytes(c->geom);
             const uint32_t lds1 = (LIT_THREADS / 16) * (ch + (uni ? 0u : cl)) * 34u + extra, lds2 = (LIT_THREADS / 16) * lit_decode2_stream_lds(lg) + extra;
             if (lds1 > 160u * 1024u || lds2 > 160u * 1024u) return fail(DIVANS_GPU_EINVAL, "the row caches chosen before do not fit the LDS next to this many context tables");
             c->blocks = std::min(blocks, c->num_cus * std::max(1u, std::min(8u, (160u * 1024u) / std::max(lds1, 1u))));
@@ -851,7 +887,7 @@ extern "C" int divans_gpu_codec_set_block_types(divans_gpu_codec* c, uint32_t n_
 extern "C" int divans_gpu_codec_set_encode_path(divans_gpu_codec* c, uint32_t path) {
     if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
     if (path > 2u) return fail(DIVANS_GPU_EINVAL, "path must be 0 (automatic), 1 (streaming) or 2 (bucketed)");
-    if (path == 2u && !c->bucket_ok && !c->bucket_mix_ok && !c->bucket_ctx_ok && !c->bucket_ctx_mix_ok && !c->bucket_mix_bt_ok)
+    if (path == 2u && c->bucket_pass == PASS_NONE)      // (a pass that exists is accepted; whether a call takes it is select_pass)
         return fail(DIVANS_GPU_EINVAL, "the bucketed encoder needs streams of at most 65536 bytes and either one stride distance of 2, 3, 4 or 8 everywhere (mixing values 5, 6, 7, "
                                        "or 8 and above) with a constant context, no mixing and speeds whose row totals stay inside i16, or mixing value 4 everywhere (with no context map and no mixing, or "
                                        "with dynamic mixing and one literal block type, or with dynamic mixing and several block types provided that no "
@@ -924,9 +960,7 @@ static int set_decoder_impl(divans_gpu_codec* c, uint32_t generation, const uint
                 sh |= shifts[i] << (8 * i);
             }
         }
-        const bool mask_in_lds = !(c->geom.mm_uniform == 0 || c->geom.mm_uniform == 4);
-        const uint32_t per_wg = 64u * lit_decode_t_stream_lds(lg2, c->mix) + 256u +
-                                (c->geom.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * c->geom.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
+        const uint32_t per_wg = 64u * lit_decode_t_stream_lds(lg2, c->mix) + 256u + config_lds_bytes(c->geom);
         const uint32_t fit = (160u * 1024u) / per_wg;
         if (fit == 0u) return fail(DIVANS_GPU_EINVAL, "these caches do not fit the 160 KB of LDS");
         uint32_t nb = blocks ? blocks : (c->blocks_t ? c->blocks_t : c->num_cus * 4u);      // default: one wave per SIMD
@@ -956,9 +990,7 @@ static int set_decoder_impl(divans_gpu_codec* c, uint32_t generation, const uint
         c->dm_log2 = lit_decode2_effective_caches(lg2, c->mix, false);   // only the cache sets that exist as kernel instances
         c->dm_shift = sh | (two_way ? 0x80000000u : 0u);
     }
-    const bool mask_in_lds = !(c->geom.mm_uniform == 0 || c->geom.mm_uniform == 4);
-    const uint32_t lds_per_wg = (LIT_THREADS / 16) * lit_decode2_stream_lds(c->dm_log2) + 256u /* byte ranks */ +
-                                (c->geom.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * c->geom.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
+    const uint32_t lds_per_wg = (LIT_THREADS / 16) * lit_decode2_stream_lds(c->dm_log2) + 256u /* byte ranks */ + config_lds_bytes(c->geom);
     const uint32_t fit = (160u * 1024u) / lds_per_wg;
     if (fit == 0u) return fail(DIVANS_GPU_EINVAL, "these caches do not fit the 160 KB of LDS");
     uint32_t nb = blocks ? blocks : c->blocks2;
@@ -1139,19 +1171,82 @@ extern "C" size_t divans_gpu_lit_encode_bound(size_t n) {
     return (bytes + 15) & ~(size_t)15;
 }
 
-// the fields BucketBatch and MixBucketBatch have in common (the per-sub-batch ones are set by bucket_sub_batches)
+// Argument checks the batch entry points share: per-stream offsets and sizes come as a pair or not at all, streams fit the codec, and
+// an output slot holds the longest coded stream the call can produce
+static int check_batch_shape(const divans_gpu_codec* c, const uint64_t* d_offsets, const uint32_t* d_sizes, uint32_t stream_len) {
+    if ((d_offsets == nullptr) != (d_sizes == nullptr)) return fail(DIVANS_GPU_EINVAL, "offsets and sizes go together");
+    if (stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "stream_len exceeds the codec's max_stream_len");
+    return 0;
+}
+static int check_out_slot(uint64_t out_slot, uint32_t longest) {
+    if (out_slot % 16 != 0 || out_slot < divans_gpu_lit_encode_bound(longest)) return fail(DIVANS_GPU_ECAP, "out_slot must be a multiple of 16 and >= divans_gpu_lit_encode_bound()");
+    return 0;
+}
+
+// the fields BucketBatch and MixBucketBatch have in common (the per-sub-batch ones are set by bucketed_pass)
 template <class Batch>
 static void fill_bucket_batch(const divans_gpu_codec* c, uint32_t stream_len, const divans_lit_segment* d_segs, Batch& k) {
     k.stream_len = stream_len; k.max_stream_len = c->max_stream_len;
-    k.pieces = bucket_pieces(c); k.slot = bucket_slot(c);
+    k.pieces = bucket_pieces(c); k.slot = bucket_slot(c); k.sf_stride = 2u * k.slot;
     k.segs = (const LitSegment*)d_segs; k.bt_first = c->geom.bt_first; k.n_btypes = c->geom.n_btypes; k.status = c->d_status;
 }
 
-// A bucketed pass works through the batch in launch sequences of at most `sub` streams, whose work arrays it reuses: whatever consumes
-// a sequence's pairs (`after`) is enqueued before the next one's kernels (`launch`).  Records ev[0] before the first kernel.
-template <class Batch, class Launch, class After>
-static int bucket_sub_batches(divans_gpu_codec* c, Batch& k, uint32_t sub, const SfView& view, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                              const uint32_t* d_in_sizes, const uint32_t* d_seg_begin, uint32_t n_streams, Launch&& launch, After&& after) {
+// The work arrays of a launch sequence of `sub` streams and the fields only one of the batch types has.  Every pass leaves its pairs
+// in place: bucket_unsort_kernel in sfs / xs[0], mix_weights_kernel over the stride model's entries in xs[0].
+static int bucket_work_arrays(divans_gpu_codec* c, bool, uint32_t& sub, BucketBatch& k) {
+    if (int rc = ensure_bucket(c, sub, k)) return rc;
+    k.sf = (uint32_t*)k.sfs;
+    k.inc = c->geom.inc0; k.lim = c->geom.lim0;
+    return 0;
+}
+static int bucket_work_arrays(divans_gpu_codec* c, bool two_models, uint32_t& sub, MixBucketBatch& k) {
+    int rc;
+    if (two_models) {
+        // as many streams per launch sequence as the device has room for: a bucket is a serial chain, and the longest
+        // ones (half a stream under one context) only stop dominating a sequence when it holds streams by the ten thousand
+        while ((rc = ensure_bucket_mix(c, sub, k)) == DIVANS_GPU_ENOMEM && sub > 1024u) { (void)hipGetLastError(); sub = (sub + 1u) / 2u; }
+    } else {      // the one-model context-keyed pass: a MixBucketBatch over the one-model layout
+        BucketBatch lay;
+        std::memset(&lay, 0, sizeof(lay));
+        rc = ensure_bucket(c, sub, lay);
+        k.counters = lay.counters; k.xs[0] = lay.sfs; k.desc = lay.desc; k.tasks = lay.tasks; k.inv = lay.inv; k.sorted = (uint16_t*)lay.sorted;   // bytes
+    }
+    if (rc) return rc;
+    k.blob = c->d_blob; k.pos_stride = bucket_slot(c);
+    k.sf = (uint32_t*)k.xs[0];
+    k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
+    return 0;
+}
+
+static int launch_bucket_pass(divans_gpu_codec* c, BucketPass, const BucketBatch& kk) {
+    if (c->bucket_stride > 1u) HIP_TRY(launch_bucket_stride_model(kk, c->bucket_stride, c->num_cus * 4u, c->stream));
+    else HIP_TRY(launch_bucket_model(kk, c->num_cus * 4u, c->stream));
+    return 0;
+}
+static int launch_bucket_pass(divans_gpu_codec* c, BucketPass pass, const MixBucketBatch& kk) {
+    if (pass == PASS_MIX) HIP_TRY(launch_bucket_mix_model(kk, c->num_cus, c->stream));
+    else if (pass == PASS_CTX_MIX) HIP_TRY(launch_bucket_ctx_mix_model(kk, c->num_cus, c->stream));
+    else if (pass == PASS_CTX) HIP_TRY(launch_bucket_ctx_model(kk, c->num_cus * 4u, c->stream));
+    else HIP_TRY(launch_bucket_mix_bt_model(kk, c->num_cus, c->stream));
+    return 0;
+}
+
+// A bucketed pass (Batch = BucketBatch for PASS_STRIDE, MixBucketBatch for the others) works through the batch in launch sequences
+// of at most bucket_mix_batch streams, whose work arrays it reuses -- 11.2 bytes per input byte of 32 768 streams, not of the batch:
+// whatever consumes a sequence's pairs (`after`) is enqueued before the next one's kernels.  Records ev[0] before the first kernel.
+template <class Batch, class After>
+static int bucketed_pass(divans_gpu_codec* c, BucketPass pass, const uint8_t* d_in, const uint64_t* d_in_offsets, const uint32_t* d_in_sizes,
+                         uint32_t stream_len, uint32_t n_streams, const uint32_t* d_seg_begin, const divans_lit_segment* d_segs, After&& after) {
+    const bool two_models = kPassTraits[pass].two_models;
+    Batch k;
+    std::memset(&k, 0, sizeof(k));
+    uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
+    if (int rc = bucket_work_arrays(c, two_models, sub, k)) return rc;
+    fill_bucket_batch(c, stream_len, d_segs, k);
+    c->last_encode_path = two_models ? 3u : 2u;
+    SfView view;
+    view.sf = k.sf; view.stride = k.sf_stride;
+    view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * (two_models ? 4u : 3u);
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     for (uint32_t s0 = 0; s0 < n_streams; s0 += sub) {
         k.n_streams = std::min(sub, n_streams - s0);
@@ -1159,117 +1254,28 @@ static int bucket_sub_batches(divans_gpu_codec* c, Batch& k, uint32_t sub, const
         k.in_offsets = d_in_offsets ? d_in_offsets + s0 : nullptr;
         k.in_sizes = d_in_sizes ? d_in_sizes + s0 : nullptr;
         k.seg_begin = d_seg_begin ? d_seg_begin + s0 : nullptr;
-        if (int rc = launch(k)) return rc;
+        if (int rc = launch_bucket_pass(c, pass, k)) return rc;
         if (int rc = after(s0, k.n_streams, view)) return rc;
     }
     return 0;
 }
 
 // Encoder pass 1: (start | freq << 16) per nibble, position order.  `after(first, count, view)` is called once the model kernels
-// of streams [first, first + count) are enqueued (the bucketed passes work through the batch in sub-batches, bucket_sub_batches);
+// of streams [first, first + count) are enqueued (the bucketed passes work through the batch in sub-batches, bucketed_pass);
 // they leave the pairs in their own work arrays (the unsort is in place), the streaming kernels in c->d_sf.  Records ev[0] first.
 template <class After>
 static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets, const uint32_t* d_in_sizes,
                       uint32_t stream_len, uint32_t n_streams, const uint32_t* d_seg_begin, const divans_lit_segment* d_segs, After&& after) {
     int rc = maybe_learn_rank(c, d_in, d_in_offsets, d_in_sizes, n_streams, stream_len);     // byte order 0: the decoder's table order follows the data the codec sees
     if (rc) return rc;
-    SfView view;
-    // segment lists (context reloads between Literal commands) go through the streaming kernels unless the caller asked for the
-    // bucketed pass (divans_gpu_codec_set_encode_path(c, 2)): its sort kernels then take the keys of a segment's first bytes from last8
-    const bool segs_ok = !d_segs || c->encode_path == 2u;
-    if (use_bucket(c) && n_streams < (1u << 24) && segs_ok) {
-        BucketBatch k;
-        std::memset(&k, 0, sizeof(k));
-        // launch sequences of at most bucket_mix_batch streams: work arrays of 11.2 bytes per input byte of 32 768 streams, not of the batch
-        const uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
-        rc = ensure_bucket(c, sub, k); if (rc) return rc;
-        fill_bucket_batch(c, stream_len, d_segs, k);
-        k.sf = (uint32_t*)k.sfs; k.sf_stride = 2u * k.slot;     // bucket_unsort_kernel works in place
-        k.inc = c->geom.inc0; k.lim = c->geom.lim0;
-        c->last_encode_path = 2u;
-        view.sf = k.sf; view.stride = k.sf_stride;
-        view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 3u;
-        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
-                                  [&](const BucketBatch& kk) -> int {
-                                      if (c->bucket_stride > 1u) HIP_TRY(launch_bucket_stride_model(kk, c->bucket_stride, c->num_cus * 4u, c->stream));
-                                      else HIP_TRY(launch_bucket_model(kk, c->num_cus * 4u, c->stream));
-                                      return 0;
-                                  }, after);
-    }
-    if (use_bucket_mix(c) && segs_ok) {
-        MixBucketBatch k;
-        std::memset(&k, 0, sizeof(k));
-        // as many streams per launch sequence as the device has room for: a bucket is a serial chain, and the longest
-        // ones (half a stream under one context) only stop dominating a sequence when it holds streams by the ten thousand
-        uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
-        while ((rc = ensure_bucket_mix(c, sub, k)) == DIVANS_GPU_ENOMEM && sub > 1024u) { (void)hipGetLastError(); sub = (sub + 1u) / 2u; }
-        if (rc) return rc;
-        fill_bucket_batch(c, stream_len, d_segs, k);
-        k.blob = c->d_blob; k.pos_stride = k.slot;
-        k.sf = (uint32_t*)k.xs[0]; k.sf_stride = 2u * k.slot;  // mix_weights_kernel writes the pairs over the stride model's entries
-        k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
-        c->last_encode_path = 3u;
-        view.sf = k.sf; view.stride = k.sf_stride;
-        view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 4u;
-        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
-                                  [&](const MixBucketBatch& kk) -> int { HIP_TRY(launch_bucket_mix_model(kk, c->num_cus, c->stream)); return 0; }, after);
-    }
-    if (use_bucket_ctx(c, d_segs != nullptr) && n_streams < (1u << 24)) {
-        // context-keyed rows (lit_bucket_ctx.hip): one sort by context for one model or two; the work arrays of the pass with the same
-        // number of models, sub-batches and status contract as above
-        MixBucketBatch k;
-        std::memset(&k, 0, sizeof(k));
-        uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
-        const bool two = c->bucket_ctx_mix_ok;
-        if (two) {
-            while ((rc = ensure_bucket_mix(c, sub, k)) == DIVANS_GPU_ENOMEM && sub > 1024u) { (void)hipGetLastError(); sub = (sub + 1u) / 2u; }
-            if (rc) return rc;
-        } else {
-            BucketBatch lay;
-            std::memset(&lay, 0, sizeof(lay));
-            rc = ensure_bucket(c, sub, lay); if (rc) return rc;
-            k.counters = lay.counters; k.xs[0] = lay.sfs; k.desc = lay.desc; k.tasks = lay.tasks; k.inv = lay.inv; k.sorted = (uint16_t*)lay.sorted;   // bytes
-        }
-        fill_bucket_batch(c, stream_len, d_segs, k);
-        k.blob = c->d_blob; k.pos_stride = k.slot;
-        k.sf = (uint32_t*)k.xs[0]; k.sf_stride = 2u * k.slot;  // in place: bucket_unsort_kernel / mix_weights_kernel leave the pairs in xs[0]
-        k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
-        c->last_encode_path = two ? 3u : 2u;
-        view.sf = k.sf; view.stride = k.sf_stride;
-        view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * (two ? 4u : 3u);
-        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
-                                  [&](const MixBucketBatch& kk) -> int {
-                                      if (two) HIP_TRY(launch_bucket_ctx_mix_model(kk, c->num_cus, c->stream));
-                                      else HIP_TRY(launch_bucket_ctx_model(kk, c->num_cus * 4u, c->stream));
-                                      return 0;
-                                  }, after);
-    }
-    if (use_bucket_mix_bt(c, d_segs != nullptr) && n_streams < (1u << 24)) {
-        // several block types under mixing value 4 (launch_bucket_mix_bt_model): the two-model pass with the block type in the stride
-        // model's high-row slot and in the context model's key; work arrays, sub-batches and status contract as above
-        MixBucketBatch k;
-        std::memset(&k, 0, sizeof(k));
-        uint32_t sub = std::min(n_streams, c->bucket_mix_batch);
-        while ((rc = ensure_bucket_mix(c, sub, k)) == DIVANS_GPU_ENOMEM && sub > 1024u) { (void)hipGetLastError(); sub = (sub + 1u) / 2u; }
-        if (rc) return rc;
-        fill_bucket_batch(c, stream_len, d_segs, k);
-        k.blob = c->d_blob; k.pos_stride = k.slot;
-        k.sf = (uint32_t*)k.xs[0]; k.sf_stride = 2u * k.slot;
-        k.inc0 = c->geom.inc0; k.lim0 = c->geom.lim0; k.inc2 = c->geom.inc2; k.lim2 = c->geom.lim2; k.inc3 = c->geom.inc3; k.lim3 = c->geom.lim3;
-        c->last_encode_path = 3u;
-        view.sf = k.sf; view.stride = k.sf_stride;
-        view.spare = (uint8_t*)k.inv; view.spare_bytes = (size_t)sub * k.slot * 4u;
-        return bucket_sub_batches(c, k, sub, view, d_in, d_in_offsets, d_in_sizes, d_seg_begin, n_streams,
-                                  [&](const MixBucketBatch& kk) -> int { HIP_TRY(launch_bucket_mix_bt_model(kk, c->num_cus, c->stream)); return 0; }, after);
-    }
+    const BucketPass pass = select_pass(c, d_segs != nullptr, n_streams);
+    if (pass == PASS_STRIDE) return bucketed_pass<BucketBatch>(c, pass, d_in, d_in_offsets, d_in_sizes, stream_len, n_streams, d_seg_begin, d_segs, after);
+    if (pass != PASS_NONE) return bucketed_pass<MixBucketBatch>(c, pass, d_in, d_in_offsets, d_in_sizes, stream_len, n_streams, d_seg_begin, d_segs, after);
     rc = ensure_sf(c, n_streams); if (rc) return rc;
     rc = ensure_tables(c); if (rc) return rc;
-    LitBatch b;
-    std::memset(&b, 0, sizeof(b));
-    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
-    b.n_streams = n_streams; b.stream_len = stream_len; b.max_stream_len = c->max_stream_len;
+    LitBatch b = lit_batch(c, n_streams, stream_len);
     b.in = d_in; b.in_offsets = d_in_offsets; b.in_sizes = d_in_sizes;
-    b.sf = c->d_sf; b.status = c->d_status;
+    b.sf = c->d_sf;
     b.seg_begin = d_seg_begin; b.segs = (const LitSegment*)d_segs;
     set_cache_fields(c, b);
     if (d_segs && b.cache_mode != 2u && b.cache_mode != 0u) return fail(DIVANS_GPU_EINVAL, "segment lists need the default (high-nibble-row) cache or none");
@@ -1277,6 +1283,7 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
     ++c->table_launch_seq;
     c->last_encode_path = 1u;
     HIP_TRY(launch_model_encode(b, c->mix, c->blocks, c->stream));
+    SfView view;
     view.sf = c->d_sf; view.stride = 2u * c->max_stream_len;
     return after(0u, n_streams, view);
 }
@@ -1338,10 +1345,8 @@ static int encode_batch_impl(divans_gpu_codec* c, const uint8_t* d_in, const uin
     if (!c || !d_in || !d_out || !d_out_offsets || !d_out_sizes) return fail(DIVANS_GPU_EINVAL, "null argument");
     if ((d_seg_begin == nullptr) != (d_segs == nullptr)) return fail(DIVANS_GPU_EINVAL, "seg_begin and segs go together");
     if (n_streams == 0) return 0;
-    if ((d_in_offsets == nullptr) != (d_in_sizes == nullptr)) return fail(DIVANS_GPU_EINVAL, "offsets and sizes go together");
-    if (stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "stream_len exceeds the codec's max_stream_len");
-    if (out_slot % 16 != 0 || out_slot < divans_gpu_lit_encode_bound(d_in_sizes ? c->max_stream_len : stream_len))
-        return fail(DIVANS_GPU_ECAP, "out_slot must be a multiple of 16 and >= divans_gpu_lit_encode_bound()");
+    if (int rc = check_batch_shape(c, d_in_offsets, d_in_sizes, stream_len)) return rc;
+    if (int rc = check_out_slot(out_slot, d_in_sizes ? c->max_stream_len : stream_len)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     size_t pairs = 0;
     int rc = model_pass(c, d_in, d_in_offsets, d_in_sizes, stream_len, n_streams, d_seg_begin, d_segs,
@@ -1361,24 +1366,15 @@ extern "C" int divans_gpu_lit_encode_packed(divans_gpu_codec* c, const uint8_t* 
                                             uint32_t stream_len, uint32_t n_streams, uint8_t* d_packed, uint64_t packed_cap,
                                             uint64_t* d_packed_offsets, uint32_t* d_sizes, uint64_t* d_total, uint32_t sub_batch) {
     if (!c || !d_in || !d_packed || !d_packed_offsets || !d_sizes || !d_total) return fail(DIVANS_GPU_EINVAL, "null argument");
-    if ((d_in_offsets == nullptr) != (d_in_sizes == nullptr)) return fail(DIVANS_GPU_EINVAL, "offsets and sizes go together");
-    if (stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "stream_len exceeds the codec's max_stream_len");
+    if (int rc = check_batch_shape(c, d_in_offsets, d_in_sizes, stream_len)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(uint64_t), c->stream));
     if (n_streams == 0) return 0;
     const uint64_t slot = divans_gpu_lit_encode_bound(d_in_sizes ? c->max_stream_len : stream_len);
     uint32_t sub = std::min(n_streams, sub_batch ? sub_batch : c->bucket_mix_batch);
     while ((uint64_t)sub * slot > ((uint64_t)1 << 36) && sub > 1024u) sub = (sub + 1u) / 2u;      // at most 64 GiB of slots
-    if ((size_t)sub * slot > c->slots_bytes) {
-        if (c->d_slots) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_slots)); c->d_slots = nullptr; c->slots_bytes = 0; }
-        if (device_alloc((void**)&c->d_slots, (size_t)sub * slot) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(output slots of a sub-batch) failed");
-        c->slots_bytes = (size_t)sub * slot;
-    }
-    if (sub > c->slot_off_cap) {
-        if (c->d_slot_off) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_slot_off)); c->d_slot_off = nullptr; c->slot_off_cap = 0; }
-        if (hipMalloc(&c->d_slot_off, (size_t)sub * sizeof(uint64_t)) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(slot offsets) failed");
-        c->slot_off_cap = sub;
-    }
+    if (int rc = grow_buffer(c, c->d_slots, c->slots_bytes, (size_t)sub * slot, "hipMalloc(output slots of a sub-batch) failed")) return rc;
+    if (int rc = grow_buffer(c, c->d_slot_off, c->slot_off_bytes, (size_t)sub * sizeof(uint64_t), "hipMalloc(slot offsets) failed")) return rc;
     const size_t n_sub = (n_streams + sub - 1u) / sub;
     while (c->ev_span.size() < 3u * n_sub) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreate(&e)); c->ev_span.push_back(e); }
     size_t pairs = 0, span = 0;
@@ -1422,8 +1418,7 @@ extern "C" int divans_gpu_lit_model_batch(divans_gpu_codec* c, const uint8_t* d_
                                           const uint32_t* d_in_sizes, uint32_t stream_len, uint32_t n_streams, uint32_t* d_pairs) {
     if (!c || !d_in || !d_pairs) return fail(DIVANS_GPU_EINVAL, "null argument");
     if (n_streams == 0) return 0;
-    if ((d_in_offsets == nullptr) != (d_in_sizes == nullptr)) return fail(DIVANS_GPU_EINVAL, "offsets and sizes go together");
-    if (stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "stream_len exceeds the codec's max_stream_len");
+    if (int rc = check_batch_shape(c, d_in_offsets, d_in_sizes, stream_len)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t row = (size_t)2u * c->max_stream_len * sizeof(uint32_t);
     int rc = model_pass(c, d_in, d_in_offsets, d_in_sizes, stream_len, n_streams, nullptr, nullptr,
@@ -1480,14 +1475,11 @@ extern "C" int divans_gpu_lit_decode_commands_batch(divans_gpu_codec* c, const u
     if (n_streams == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_tables(c); if (rc) return rc;
-    LitBatch b;
-    std::memset(&b, 0, sizeof(b));
-    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
-    b.n_streams = n_streams; b.stream_len = lit_stream_len; b.max_stream_len = c->max_stream_len;
+    LitBatch b = lit_batch(c, n_streams, lit_stream_len);
     b.in = d_in; b.in_offsets = d_in_offsets; b.in_sizes = d_in_sizes;
-    b.out = d_raw; b.out_offsets = d_raw_offsets; b.out_sizes = d_raw_sizes; b.status = c->d_status;
+    b.out = d_raw; b.out_offsets = d_raw_offsets; b.out_sizes = d_raw_sizes;
     b.stream_bad = c->d_stream_flags;
-    b.byte_rank = (c->byte_order != 1u && c->rank_ready) ? c->d_rank : nullptr;
+    b.byte_rank = byte_rank_of(c);
     // the high-row caches in the 2-way organisation, or none: a subset of what the codec's grid was sized for
     b.dm_log2 = lit_decode2_commands_caches(c->dm_log2, c->mix, c->geom.total_rows);
     b.dm_shift = (c->dm_shift & 0x1f1f1f1fu) | 0x80000000u;
@@ -1523,8 +1515,7 @@ extern "C" int divans_gpu_lit_encode_commands_batch(divans_gpu_codec* c, const u
         return fail(DIVANS_GPU_EINVAL, "insert bytes, their offsets and their sizes go together");
     if (lit_stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "lit_stream_len exceeds the codec's max_stream_len");
     if (c->sp_started || c->sd_started) return fail(DIVANS_GPU_EINVAL, "a stream coded call by call is open on this codec");
-    if (out_slot % 16 != 0 || out_slot < divans_gpu_lit_encode_bound(c->max_stream_len))      // what encode_batch_impl refuses, before anything is launched
-        return fail(DIVANS_GPU_ECAP, "out_slot must be a multiple of 16 and >= divans_gpu_lit_encode_bound()");
+    if (int rc = check_out_slot(out_slot, c->max_stream_len)) return rc;      // what encode_batch_impl refuses, before anything is launched
     if (n_streams == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     uint32_t ends[2] = {0u, 0u};
@@ -1537,11 +1528,7 @@ extern "C" int divans_gpu_lit_encode_commands_batch(divans_gpu_codec* c, const u
     // [segments: 16 per command, at least one][literal offsets: 8 n, rounded up to 16][literal slots: lit_slot n][literal sizes: 4 n][segment begins: 4 (n + 1)]
     const size_t sz_segs = std::max<size_t>(n_cmds, 1u) * sizeof(LitSegment), sz_off = (n * sizeof(uint64_t) + 15u) & ~(size_t)15u, sz_lit = n * (size_t)lit_slot;
     const size_t need = sz_segs + sz_off + sz_lit + n * sizeof(uint32_t) + (n + 1u) * sizeof(uint32_t);
-    if (need > c->cp_bytes) {
-        if (c->d_cp) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_cp)); c->d_cp = nullptr; c->cp_bytes = 0; }
-        if (device_alloc((void**)&c->d_cp, need) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(work arrays of the command lists) failed");
-        c->cp_bytes = need;
-    }
+    if (int rc = grow_buffer(c, c->d_cp, c->cp_bytes, need, "hipMalloc(work arrays of the command lists) failed")) return rc;
     for (auto& e : c->ev_cp) if (!e) HIP_TRY(hipEventCreate(&e));
     LitCommandPrepare p;
     std::memset(&p, 0, sizeof(p));
@@ -1591,8 +1578,7 @@ static void decode2_shape(divans_gpu_codec* c, uint32_t n_streams, bool segs, Li
         // 32 high rows, 8192: 44.5 -> 40.4; mixing 20 480 streams 162.8 -> 152.5 ms with 32 + 16, 16 384: 134.4 -> 123.4 with 32 + 32;
         // low-row caches do not pay even there)
         if (!segs && c->geom.total_rows < 0x7fffu) {
-            const bool mask_in_lds = !(c->geom.mm_uniform == 0 || c->geom.mm_uniform == 4);
-            const uint32_t fixed = 256u + (c->geom.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * c->geom.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
+            const uint32_t fixed = 256u + config_lds_bytes(c->geom);
             const uint32_t mix_cands[2] = {6u | (6u << 8), 6u | (5u << 8)};      // (log2 rows + 1) per table: high stride | FirstNibble << 8
             const uint32_t plain_cands[1] = {7u};
             const uint32_t* cands = c->mix ? mix_cands : plain_cands;
@@ -1669,8 +1655,7 @@ static int decode_batch_impl(divans_gpu_codec* c, const uint8_t* d_in, const uin
                              const uint32_t* d_seg_begin, const divans_lit_segment* d_segs) {
     if (!c || !d_in || !d_in_offsets || !d_in_sizes || !d_out) return fail(DIVANS_GPU_EINVAL, "null argument");
     if (n_streams == 0) return 0;
-    if ((d_out_offsets == nullptr) != (d_out_sizes == nullptr)) return fail(DIVANS_GPU_EINVAL, "offsets and sizes go together");
-    if (stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "stream_len exceeds the codec's max_stream_len");
+    if (int rc = check_batch_shape(c, d_out_offsets, d_out_sizes, stream_len)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_tables(c); if (rc) return rc;
     // The table placements are compared on launches that differ in nothing else: the byte order is settled first (order 0 learns it from
@@ -1682,15 +1667,12 @@ static int decode_batch_impl(divans_gpu_codec* c, const uint8_t* d_in, const uin
     const bool eager = c->eager_tune;                   // divans_gpu_codec_tune_tables(c, k >= 2): every placement on this call
     bool measure = false;
     if (qualifies && !eager) { rc = placement_step(c, want, n_streams, stream_len, &measure); if (rc) return rc; }
-    LitBatch b;
-    std::memset(&b, 0, sizeof(b));
-    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
-    b.n_streams = n_streams; b.stream_len = stream_len; b.max_stream_len = c->max_stream_len;
+    LitBatch b = lit_batch(c, n_streams, stream_len);
     b.in = d_in; b.in_offsets = d_in_offsets; b.in_sizes = d_in_sizes;
-    b.out = d_out; b.out_offsets = d_out_offsets; b.out_sizes = d_out_sizes; b.status = c->d_status;
+    b.out = d_out; b.out_offsets = d_out_offsets; b.out_sizes = d_out_sizes;
     b.stream_bad = c->d_stream_flags;
     b.seg_begin = d_seg_begin; b.segs = (const LitSegment*)d_segs;
-    b.byte_rank = (c->byte_order != 1u && c->rank_ready) ? c->d_rank : nullptr;
+    b.byte_rank = byte_rank_of(c);
     set_cache_fields(c, b);
 #if !DIVANS_WITH_EXPERIMENTAL_DECODERS
     if (!use_decode2(c) && (b.cache_mode == 1u || b.cache_mode == 3u)) {     // the generation-1 fallback of this build knows the high-row cache or none
@@ -1776,12 +1758,9 @@ extern "C" int divans_gpu_codec_row_replay(divans_gpu_codec* c, const uint8_t* d
     if (!use_decode2(c) || c->geom.mm_uniform != 4) return fail(DIVANS_GPU_EINVAL, "row replay exists for the stride-1 configurations of the second-generation decoder");
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_tables(c); if (rc) return rc;
-    LitBatch b;
-    std::memset(&b, 0, sizeof(b));
-    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
-    b.n_streams = n_streams; b.stream_len = stream_len; b.max_stream_len = c->max_stream_len;
+    LitBatch b = lit_batch(c, n_streams, stream_len);      // (the replay kernels report nothing: they never touch the status word)
     b.in = d_literals; b.in_offsets = d_offsets; b.in_sizes = d_sizes;
-    b.byte_rank = (c->byte_order != 1u && c->rank_ready) ? c->d_rank : nullptr;
+    b.byte_rank = byte_rank_of(c);
     uint32_t grid = 0;
     decode2_shape(c, n_streams, false, b, grid);
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
@@ -2050,12 +2029,8 @@ extern "C" int divans_gpu_lit_encode_host(divans_gpu_codec* c, const uint8_t* in
 // The host-buffer entry points keep their device buffers between calls (allocating and freeing gigabytes per call
 // costs more than the kernels); `which` names the buffer, capacity only grows.
 template <typename T>
-static int host_scratch(divans_gpu_codec* c, int which, size_t bytes, T** out) {
-    if (bytes > c->host_scratch_cap[which]) {
-        if (c->host_scratch[which]) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->host_scratch[which])); c->host_scratch[which] = nullptr; c->host_scratch_cap[which] = 0; }
-        if (device_alloc((void**)&c->host_scratch[which], bytes) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(host-buffer staging) failed");
-        c->host_scratch_cap[which] = bytes;
-    }
+static int host_scratch(divans_gpu_codec* c, HostBuf which, size_t bytes, T** out) {
+    if (int rc = grow_buffer(c, c->host_scratch[which], c->host_scratch_cap[which], bytes, "hipMalloc(host-buffer staging) failed")) return rc;
     *out = (T*)c->host_scratch[which];
     return 0;
 }
@@ -2072,9 +2047,9 @@ static int stream_rans(divans_gpu_codec* c, uint32_t n_chunks, uint32_t syms_las
     const uint64_t slot = divans_gpu_lit_encode_bound(32768);
     uint8_t* d_out = nullptr; uint64_t* d_off = nullptr; uint32_t* d_sz = nullptr; uint32_t* d_len = nullptr;
     int rc;
-    if ((rc = host_scratch(c, 4, (size_t)n_chunks * slot + 64, &d_out))) return rc;
-    if ((rc = host_scratch(c, 5, (size_t)n_chunks * 8u + 64, &d_off))) return rc;
-    if ((rc = host_scratch(c, 6, (size_t)n_chunks * 8u + 64, &d_sz))) return rc;
+    if ((rc = host_scratch(c, HB_CHUNK_SLOTS, (size_t)n_chunks * slot + 64, &d_out))) return rc;
+    if ((rc = host_scratch(c, HB_CHUNK_OFFSETS, (size_t)n_chunks * 8u + 64, &d_off))) return rc;
+    if ((rc = host_scratch(c, HB_SIZES, (size_t)n_chunks * 8u + 64, &d_sz))) return rc;
     d_len = d_sz + n_chunks;
     std::vector<uint32_t> lens(n_chunks, 32768u); lens[n_chunks - 1] = syms_last / 2u;
     HIP_TRY(hipMemcpyAsync(d_len, lens.data(), (size_t)n_chunks * 4u, hipMemcpyHostToDevice, c->stream));
@@ -2125,16 +2100,13 @@ extern "C" int divans_gpu_lit_stream_encode(divans_gpu_codec* c, const uint8_t* 
         c->d_sp = p; c->sp_cap = need;
     }
     uint8_t* d_in = nullptr; uint32_t* d_seg = nullptr;
-    if ((rc = host_scratch(c, 0, (size_t)len + 64, &d_in))) return rc;
-    if ((rc = host_scratch(c, 7, 64, &d_seg))) return rc;
+    if ((rc = host_scratch(c, HB_IN, (size_t)len + 64, &d_in))) return rc;
+    if ((rc = host_scratch(c, HB_META, 64, &d_seg))) return rc;
     const uint32_t seg_host[8] = {0u, 1u, 0u, 0u, len, (uint32_t)c->cfg.btype, (uint32_t)last8, (uint32_t)(last8 >> 32)};   // seg_begin[2], pad, divans_lit_segment
     HIP_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_seg, seg_host, sizeof(seg_host), hipMemcpyHostToDevice, c->stream));
-    LitBatch b;
-    std::memset(&b, 0, sizeof(b));
-    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
-    b.n_streams = 1; b.stream_len = len; b.max_stream_len = c->max_stream_len;
-    b.in = d_in; b.sf = c->d_sp + c->sp_pending; b.status = c->d_status;
+    LitBatch b = lit_batch(c, 1u, len);
+    b.in = d_in; b.sf = c->d_sp + c->sp_pending;
     b.seg_begin = d_seg; b.segs = (const LitSegment*)(d_seg + 4);
     b.resume = c->sp_started ? 1u : 0u; b.wstate = c->d_wstate;
     set_cache_fields(c, b);
@@ -2175,20 +2147,17 @@ extern "C" int divans_gpu_lit_stream_decode(divans_gpu_codec* c, const uint8_t* 
     int rc = ensure_tables(c); if (rc) return rc;
     const size_t use = std::min<size_t>(coded_bytes & ~(size_t)3, (size_t)0xfffffff0u);
     uint8_t* d_in = nullptr; uint8_t* d_out = nullptr; uint32_t* d_meta = nullptr;
-    if ((rc = host_scratch(c, 0, use + 64, &d_in))) return rc;
-    if ((rc = host_scratch(c, 1, (size_t)out_len + 64, &d_out))) return rc;
-    if ((rc = host_scratch(c, 7, 128, &d_meta))) return rc;
+    if ((rc = host_scratch(c, HB_IN, use + 64, &d_in))) return rc;
+    if ((rc = host_scratch(c, HB_DECODED, (size_t)out_len + 64, &d_out))) return rc;
+    if ((rc = host_scratch(c, HB_META, 128, &d_meta))) return rc;
     // d_meta: [0..1] in_offset (u64 0), [2] in_size, [3] consumed, [4..5] seg_begin, [8..11] divans_lit_segment
     const uint32_t meta[12] = {0u, 0u, (uint32_t)use, 0u, 0u, 1u, 0u, 0u, out_len, (uint32_t)c->cfg.btype, (uint32_t)last8, (uint32_t)(last8 >> 32)};
     HIP_TRY(hipMemcpyAsync(d_in, coded, use, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_meta, meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_status, 0, 4, c->stream));
-    LitBatch b;
-    std::memset(&b, 0, sizeof(b));
-    b.blob = c->d_blob; b.geom = c->geom; b.tables = c->d_tables;
-    b.n_streams = 1; b.stream_len = out_len; b.max_stream_len = c->max_stream_len;
+    LitBatch b = lit_batch(c, 1u, out_len);
     b.in = d_in; b.in_offsets = (const uint64_t*)d_meta; b.in_sizes = d_meta + 2; b.consumed = d_meta + 3;
-    b.out = d_out; b.status = c->d_status;
+    b.out = d_out;
     b.seg_begin = d_meta + 4; b.segs = (const LitSegment*)(d_meta + 8);
     b.resume = c->sd_started ? 1u : 0u; b.wstate = c->d_wstate;
     set_cache_fields(c, b);
@@ -2231,38 +2200,35 @@ extern "C" int divans_gpu_lit_encode_host_chunks(divans_gpu_codec* c, const uint
     uint8_t *d_in = nullptr, *d_slots = nullptr, *d_packed = nullptr;
     uint64_t *d_off = nullptr, *d_poff = nullptr, *d_total = nullptr; uint32_t* d_sz = nullptr; uint32_t* d_chunks = nullptr;
     int rc = 0;
-    auto cleanup = [&]() {};
-#define TRY_OR_CLEAN(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(DIVANS_GPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    if ((rc = host_scratch(c, 0, in_bytes + 64, &d_in))) return rc;
-    if ((rc = host_scratch(c, 1, slot * n_streams + 64, &d_slots))) return rc;
-    if ((rc = host_scratch(c, 2, slot * n_streams + 64, &d_packed))) return rc;
-    if ((rc = host_scratch(c, 3, sizeof(uint64_t) * n_streams, &d_off))) return rc;
-    if ((rc = host_scratch(c, 4, sizeof(uint64_t) * n_streams, &d_poff))) return rc;
-    if ((rc = host_scratch(c, 5, sizeof(uint64_t), &d_total))) return rc;
-    if ((rc = host_scratch(c, 6, sizeof(uint32_t) * n_streams, &d_sz))) return rc;
+    if ((rc = host_scratch(c, HB_IN, in_bytes + 64, &d_in))) return rc;
+    if ((rc = host_scratch(c, HB_SLOTS, slot * n_streams + 64, &d_slots))) return rc;
+    if ((rc = host_scratch(c, HB_PACKED, slot * n_streams + 64, &d_packed))) return rc;
+    if ((rc = host_scratch(c, HB_OFFSETS, sizeof(uint64_t) * n_streams, &d_off))) return rc;
+    if ((rc = host_scratch(c, HB_PACKED_OFFSETS, sizeof(uint64_t) * n_streams, &d_poff))) return rc;
+    if ((rc = host_scratch(c, HB_TOTALS, sizeof(uint64_t), &d_total))) return rc;
+    if ((rc = host_scratch(c, HB_SIZES, sizeof(uint32_t) * n_streams, &d_sz))) return rc;
     if (out_chunk_bytes) {
-        if ((rc = host_scratch(c, 7, sizeof(uint32_t) * (size_t)n_streams * max_chunks, &d_chunks))) return rc;
-        TRY_OR_CLEAN(hipMemsetAsync(d_chunks, 0, sizeof(uint32_t) * (size_t)n_streams * max_chunks, c->stream));
+        if ((rc = host_scratch(c, HB_CHUNK_BYTES, sizeof(uint32_t) * (size_t)n_streams * max_chunks, &d_chunks))) return rc;
+        HIP_TRY(hipMemsetAsync(d_chunks, 0, sizeof(uint32_t) * (size_t)n_streams * max_chunks, c->stream));
     }
-    TRY_OR_CLEAN(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream));   // this call reports only its own status
-    TRY_OR_CLEAN(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream));   // this call reports only its own status
+    HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
     rc = encode_batch_impl(c, d_in, nullptr, nullptr, stream_len, n_streams, d_slots, slot, d_off, d_sz, d_chunks, max_chunks);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     rc = divans_gpu_pack_streams(c, d_slots, d_off, d_sz, n_streams, d_packed, d_poff, d_total);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     uint64_t total = 0; uint32_t status = 0;
-    TRY_OR_CLEAN(hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    TRY_OR_CLEAN(hipMemcpyAsync(&status, c->d_status, sizeof(status), hipMemcpyDeviceToHost, c->stream));
-    TRY_OR_CLEAN(hipMemcpyAsync(out_offsets, d_poff, sizeof(uint64_t) * n_streams, hipMemcpyDeviceToHost, c->stream));
-    TRY_OR_CLEAN(hipMemcpyAsync(out_sizes, d_sz, sizeof(uint32_t) * n_streams, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&status, c->d_status, sizeof(status), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_offsets, d_poff, sizeof(uint64_t) * n_streams, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_sizes, d_sz, sizeof(uint32_t) * n_streams, hipMemcpyDeviceToHost, c->stream));
     if (out_chunk_bytes)
-        TRY_OR_CLEAN(hipMemcpyAsync(out_chunk_bytes, d_chunks, sizeof(uint32_t) * (size_t)n_streams * max_chunks, hipMemcpyDeviceToHost, c->stream));
-    TRY_OR_CLEAN(hipStreamSynchronize(c->stream));
-    if (status) { (void)hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream); cleanup(); return fail(DIVANS_GPU_EINVAL, "model produced an invalid (start,freq): unsupported speed/CDF state"); }
-    if (total > out_cap) { cleanup(); return fail(DIVANS_GPU_ECAP, "out_cap too small for the packed streams"); }
-    TRY_OR_CLEAN(hipMemcpy(out_packed, d_packed, total, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpyAsync(out_chunk_bytes, d_chunks, sizeof(uint32_t) * (size_t)n_streams * max_chunks, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (status) { (void)hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream); return fail(DIVANS_GPU_EINVAL, "model produced an invalid (start,freq): unsupported speed/CDF state"); }
+    if (total > out_cap) return fail(DIVANS_GPU_ECAP, "out_cap too small for the packed streams");
+    HIP_TRY(hipMemcpy(out_packed, d_packed, total, hipMemcpyDeviceToHost));
     *out_total = total;
-    cleanup();
     return 0;
 }
 
@@ -2276,23 +2242,21 @@ extern "C" int divans_gpu_lit_decode_host(divans_gpu_codec* c, const uint8_t* in
         total = std::max<size_t>(total, in_offsets[i] + in_sizes[i]);
     }
     uint8_t *d_in = nullptr, *d_out = nullptr; uint64_t* d_off = nullptr; uint32_t* d_sz = nullptr;
-    auto cleanup = [&]() {};
     int rc0 = 0;
-    if ((rc0 = host_scratch(c, 0, total + 128, &d_in))) return rc0;
-    if ((rc0 = host_scratch(c, 1, (size_t)stream_len * n_streams + 64, &d_out))) return rc0;
-    if ((rc0 = host_scratch(c, 3, sizeof(uint64_t) * n_streams, &d_off))) return rc0;
-    if ((rc0 = host_scratch(c, 6, sizeof(uint32_t) * n_streams, &d_sz))) return rc0;
-    TRY_OR_CLEAN(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream));   // this call reports only its own status
-    TRY_OR_CLEAN(hipMemcpyAsync(d_in, in_packed, total, hipMemcpyHostToDevice, c->stream));
-    TRY_OR_CLEAN(hipMemcpyAsync(d_off, in_offsets, sizeof(uint64_t) * n_streams, hipMemcpyHostToDevice, c->stream));
-    TRY_OR_CLEAN(hipMemcpyAsync(d_sz, in_sizes, sizeof(uint32_t) * n_streams, hipMemcpyHostToDevice, c->stream));
+    if ((rc0 = host_scratch(c, HB_IN, total + 128, &d_in))) return rc0;
+    if ((rc0 = host_scratch(c, HB_DECODED, (size_t)stream_len * n_streams + 64, &d_out))) return rc0;
+    if ((rc0 = host_scratch(c, HB_OFFSETS, sizeof(uint64_t) * n_streams, &d_off))) return rc0;
+    if ((rc0 = host_scratch(c, HB_SIZES, sizeof(uint32_t) * n_streams, &d_sz))) return rc0;
+    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream));   // this call reports only its own status
+    HIP_TRY(hipMemcpyAsync(d_in, in_packed, total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_off, in_offsets, sizeof(uint64_t) * n_streams, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_sz, in_sizes, sizeof(uint32_t) * n_streams, hipMemcpyHostToDevice, c->stream));
     int rc = divans_gpu_lit_decode_batch(c, d_in, d_off, d_sz, n_streams, d_out, nullptr, nullptr, stream_len);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     uint32_t status = 0;
-    TRY_OR_CLEAN(hipMemcpyAsync(&status, c->d_status, sizeof(status), hipMemcpyDeviceToHost, c->stream));
-    TRY_OR_CLEAN(hipMemcpyAsync(out, d_out, (size_t)stream_len * n_streams, hipMemcpyDeviceToHost, c->stream));
-    TRY_OR_CLEAN(hipStreamSynchronize(c->stream));
-    cleanup();
+    HIP_TRY(hipMemcpyAsync(&status, c->d_status, sizeof(status), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)stream_len * n_streams, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     if (status & LIT_STATUS_BAD_STREAM) {
         (void)hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream);
         return fail(DIVANS_GPU_ECORRUPT, "a coded stream is truncated, corrupt or was coded under another configuration (final rANS states / word count mismatch)");
@@ -2344,13 +2308,13 @@ extern "C" int divans_gpu_lit_encode_host_pipelined(divans_gpu_codec* c, const u
     uint64_t *d_off = nullptr, *d_poff = nullptr, *d_total = nullptr; uint32_t* d_sz = nullptr;
     int rc = 0;
     if ((rc = ensure_pipeline(c, slices))) return rc;
-    if ((rc = host_scratch(c, 0, (size_t)stream_len * n_streams + 64, &d_in))) return rc;
-    if ((rc = host_scratch(c, 1, slot * S + 64, &d_slots))) return rc;                       // one slice of right-aligned slots
-    if ((rc = host_scratch(c, 2, slot * n_streams + 64, &d_packed))) return rc;              // every slice's packed bytes, slice i at i * S * slot
-    if ((rc = host_scratch(c, 3, sizeof(uint64_t) * n_streams, &d_off))) return rc;
-    if ((rc = host_scratch(c, 4, sizeof(uint64_t) * n_streams, &d_poff))) return rc;
-    if ((rc = host_scratch(c, 5, sizeof(uint64_t) * slices, &d_total))) return rc;
-    if ((rc = host_scratch(c, 6, sizeof(uint32_t) * n_streams, &d_sz))) return rc;
+    if ((rc = host_scratch(c, HB_IN, (size_t)stream_len * n_streams + 64, &d_in))) return rc;
+    if ((rc = host_scratch(c, HB_SLOTS, slot * S + 64, &d_slots))) return rc;                       // one slice of right-aligned slots
+    if ((rc = host_scratch(c, HB_PACKED, slot * n_streams + 64, &d_packed))) return rc;              // every slice's packed bytes, slice i at i * S * slot
+    if ((rc = host_scratch(c, HB_OFFSETS, sizeof(uint64_t) * n_streams, &d_off))) return rc;
+    if ((rc = host_scratch(c, HB_PACKED_OFFSETS, sizeof(uint64_t) * n_streams, &d_poff))) return rc;
+    if ((rc = host_scratch(c, HB_TOTALS, sizeof(uint64_t) * slices, &d_total))) return rc;
+    if ((rc = host_scratch(c, HB_SIZES, sizeof(uint32_t) * n_streams, &d_sz))) return rc;
     HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));      // earlier work on the codec's stream may still read the staging buffers
     // From here on copies from `in` and into the caller's output arrays are in flight on three streams: every exit -- also the
@@ -2420,10 +2384,10 @@ extern "C" int divans_gpu_lit_decode_host_pipelined(divans_gpu_codec* c, const u
     uint8_t *d_in = nullptr, *d_out = nullptr; uint64_t* d_off = nullptr; uint32_t* d_sz = nullptr;
     int rc = 0;
     if ((rc = ensure_pipeline(c, slices))) return rc;
-    if ((rc = host_scratch(c, 0, total + 128, &d_in))) return rc;
-    if ((rc = host_scratch(c, 1, (size_t)stream_len * n_streams + 64, &d_out))) return rc;
-    if ((rc = host_scratch(c, 3, sizeof(uint64_t) * n_streams, &d_off))) return rc;
-    if ((rc = host_scratch(c, 6, sizeof(uint32_t) * n_streams, &d_sz))) return rc;
+    if ((rc = host_scratch(c, HB_IN, total + 128, &d_in))) return rc;
+    if ((rc = host_scratch(c, HB_DECODED, (size_t)stream_len * n_streams + 64, &d_out))) return rc;
+    if ((rc = host_scratch(c, HB_OFFSETS, sizeof(uint64_t) * n_streams, &d_off))) return rc;
+    if ((rc = host_scratch(c, HB_SIZES, sizeof(uint32_t) * n_streams, &d_sz))) return rc;
     HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     auto drain = [&]() { (void)hipStreamSynchronize(c->s_in); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->s_out); };
