@@ -212,6 +212,8 @@ def load_library():
     L.divans_ir_literal_segments.argtypes = [vp, vp, sz, vp, sz]
     L.divans_gpu_lit_decode_commands_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     L.divans_gpu_lit_encode_commands_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp]
+    L.divans_gpu_lit_decode_commands_history_batch.argtypes = L.divans_gpu_lit_decode_commands_batch.argtypes + [vp, vp, vp]
+    L.divans_gpu_lit_encode_commands_history_batch.argtypes = L.divans_gpu_lit_encode_commands_batch.argtypes + [vp, vp, vp]
     L.divans_gpu_codec_last_prepare_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.divans_gpu_codec_set_stream_flags.argtypes = [vp, vp]
     for name in ("divans_ir_num_device_commands", "divans_ir_insert_size"):
@@ -245,6 +247,7 @@ def exported_symbols():
         "divans_gpu_selftest_division", "divans_gpu_speed_supported", "divans_gpu_speed_accepted", "divans_gpu_codec_status", "divans_gpu_codec_clear_status", "divans_gpu_codec_status_async", "divans_gpu_codec_last_decode_kernel", "divans_gpu_codec_set_stream_flags", "divans_gpu_codec_set_block_types",
         "divans_gpu_lit_encode_segments_batch", "divans_gpu_lit_decode_segments_batch", "divans_gpu_lit_decode_commands_batch",
         "divans_gpu_lit_encode_commands_batch", "divans_gpu_codec_last_prepare_ms",
+        "divans_gpu_lit_decode_commands_history_batch", "divans_gpu_lit_encode_commands_history_batch",
         "divans_gpu_selftest_cdf_ops", "divans_gpu_selftest_cdf_ops_on", "divans_gpu_selftest_rans_pairs", "divans_gpu_selftest_rans_batch", "divans_gpu_lit_encode_batch_chunks",
         "divans_gpu_lit_encode_host_pipelined", "divans_gpu_lit_decode_host_pipelined", "divans_gpu_host_alloc", "divans_gpu_host_free",
         "divans_gpu_lit_stream_begin", "divans_gpu_lit_stream_encode", "divans_gpu_lit_stream_finish",
@@ -636,26 +639,38 @@ class LiteralCodec:
             d_out.data_ptr(), out_offsets.data_ptr(), out_sizes.data_ptr(), int(stream_len)), "divans_gpu_lit_decode_segments_batch")
 
     def decode_commands_batch(self, d_coded, d_offsets, d_sizes, n_streams, cmd_begin, cmds, lit_sizes, lit_stream_len, d_raw, raw_offsets,
-                              raw_sizes, ins=None, ins_offsets=None, ins_sizes=None):
+                              raw_sizes, ins=None, ins_offsets=None, ins_sizes=None, hist=None, hist_offsets=None, hist_sizes=None):
         """General streams from their command lists (device tensors: cmd_begin int32[n+1], cmds uint8 view of the 16-byte
         divans_lit_command records, lit_sizes int32[n]; ins / ins_offsets / ins_sizes all None when no stream has an INSERT command):
-        the kernel runs the Copy / Insert commands itself and writes every stream's raw bytes at raw_offsets[i]."""
+        the kernel runs the Copy / Insert commands itself and writes every stream's raw bytes at raw_offsets[i].
+        hist uint8[], hist_offsets int64[n], hist_sizes int32[n] (any of them given: divans_gpu_lit_decode_commands_history_batch):
+        the bytes that lie logically in front of every stream's output, which its copies may reach and its first literals see."""
         p = lambda t: t.data_ptr() if t is not None else None
-        _check(self._lib.divans_gpu_lit_decode_commands_batch(
-            self._h, d_coded.data_ptr(), d_offsets.data_ptr(), d_sizes.data_ptr(), int(n_streams), cmd_begin.data_ptr(), cmds.data_ptr(),
-            lit_sizes.data_ptr(), int(lit_stream_len), p(ins), p(ins_offsets), p(ins_sizes), d_raw.data_ptr(), raw_offsets.data_ptr(),
-            raw_sizes.data_ptr()), "divans_gpu_lit_decode_commands_batch")
+        args = (self._h, d_coded.data_ptr(), d_offsets.data_ptr(), d_sizes.data_ptr(), int(n_streams), cmd_begin.data_ptr(), cmds.data_ptr(),
+                lit_sizes.data_ptr(), int(lit_stream_len), p(ins), p(ins_offsets), p(ins_sizes), d_raw.data_ptr(), raw_offsets.data_ptr(),
+                raw_sizes.data_ptr())
+        if hist is None and hist_offsets is None and hist_sizes is None:
+            _check(self._lib.divans_gpu_lit_decode_commands_batch(*args), "divans_gpu_lit_decode_commands_batch")
+        else:
+            _check(self._lib.divans_gpu_lit_decode_commands_history_batch(*args, p(hist), p(hist_offsets), p(hist_sizes)),
+                   "divans_gpu_lit_decode_commands_history_batch")
 
     def encode_commands_batch(self, d_raw, raw_offsets, raw_sizes, n_streams, cmd_begin, cmds, lit_stream_len, outputs, lit_sizes,
-                              ins=None, ins_offsets=None, ins_sizes=None):
+                              ins=None, ins_offsets=None, ins_sizes=None, hist=None, hist_offsets=None, hist_sizes=None):
         """General streams from their raw bytes and command lists (device tensors as decode_commands_batch takes them; `outputs` as
         encode_segments_batch): the device derives literals and segments, checks that the Copy / Insert commands reproduce the raw
-        bytes and codes the literals; lit_sizes int32[n] receives every stream's literal bytes, what decode_commands_batch is told."""
+        bytes and codes the literals; lit_sizes int32[n] receives every stream's literal bytes, what decode_commands_batch is told.
+        hist / hist_offsets / hist_sizes as decode_commands_batch takes them (divans_gpu_lit_encode_commands_history_batch); here
+        `hist` may be d_raw itself."""
         p = lambda t: t.data_ptr() if t is not None else None
-        _check(self._lib.divans_gpu_lit_encode_commands_batch(
-            self._h, d_raw.data_ptr(), raw_offsets.data_ptr(), raw_sizes.data_ptr(), int(n_streams), cmd_begin.data_ptr(), cmds.data_ptr(),
-            int(lit_stream_len), p(ins), p(ins_offsets), p(ins_sizes), outputs["out"].data_ptr(), int(outputs["slot"]),
-            outputs["offsets"].data_ptr(), outputs["sizes"].data_ptr(), lit_sizes.data_ptr()), "divans_gpu_lit_encode_commands_batch")
+        args = (self._h, d_raw.data_ptr(), raw_offsets.data_ptr(), raw_sizes.data_ptr(), int(n_streams), cmd_begin.data_ptr(), cmds.data_ptr(),
+                int(lit_stream_len), p(ins), p(ins_offsets), p(ins_sizes), outputs["out"].data_ptr(), int(outputs["slot"]),
+                outputs["offsets"].data_ptr(), outputs["sizes"].data_ptr(), lit_sizes.data_ptr())
+        if hist is None and hist_offsets is None and hist_sizes is None:
+            _check(self._lib.divans_gpu_lit_encode_commands_batch(*args), "divans_gpu_lit_encode_commands_batch")
+        else:
+            _check(self._lib.divans_gpu_lit_encode_commands_history_batch(*args, p(hist), p(hist_offsets), p(hist_sizes)),
+                   "divans_gpu_lit_encode_commands_history_batch")
 
     def last_prepare_ms(self):
         """device time of the prepare kernel inside the last encode_commands_batch call"""

@@ -1459,16 +1459,20 @@ static_assert(DIVANS_GPU_STATUS_BAD_COMMAND == LIT_STATUS_BAD_COMMAND, "status b
 
 // General streams decoded from their command lists: one launch of a lit_decode2_cmd_kernel instance, which runs the Copy / Insert
 // commands itself.  The launch is of another shape than any divans_gpu_lit_decode_batch call (raw output, its own kernels): it decodes on
-// the table placement in use and is never one of the placement search's measurements.
-extern "C" int divans_gpu_lit_decode_commands_batch(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                                                    const uint32_t* d_in_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
-                                                    const divans_lit_command* d_cmds, const uint32_t* d_lit_sizes, uint32_t lit_stream_len,
-                                                    const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
-                                                    uint8_t* d_raw, const uint64_t* d_raw_offsets, const uint32_t* d_raw_sizes) {
+// the table placement in use and is never one of the placement search's measurements.  The history triple (all null: none) is that of
+// divans_gpu_lit_decode_commands_history_batch: both entry points are this function.
+static int decode_commands_impl(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                const uint32_t* d_in_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                const divans_lit_command* d_cmds, const uint32_t* d_lit_sizes, uint32_t lit_stream_len,
+                                const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                uint8_t* d_raw, const uint64_t* d_raw_offsets, const uint32_t* d_raw_sizes,
+                                const uint8_t* d_hist, const uint64_t* d_hist_offsets, const uint32_t* d_hist_sizes) {
     if (!c || !d_in || !d_in_offsets || !d_in_sizes || !d_cmd_begin || !d_cmds || !d_lit_sizes || !d_raw || !d_raw_offsets || !d_raw_sizes)
         return fail(DIVANS_GPU_EINVAL, "null argument");
     if ((d_ins == nullptr) != (d_ins_offsets == nullptr) || (d_ins == nullptr) != (d_ins_sizes == nullptr))
         return fail(DIVANS_GPU_EINVAL, "insert bytes, their offsets and their sizes go together");
+    if ((d_hist == nullptr) != (d_hist_offsets == nullptr) || (d_hist == nullptr) != (d_hist_sizes == nullptr))
+        return fail(DIVANS_GPU_EINVAL, "history bytes, their offsets and their sizes go together");
     if (lit_stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "lit_stream_len exceeds the codec's max_stream_len");
     if (!use_decode2(c)) return fail(DIVANS_GPU_EINVAL, "command lists need decoder generation 2 or 3 (this codec decodes with generation 1: a speed whose row totals leave i16, or divans_gpu_codec_set_decoder)");
     if (c->sp_started || c->sd_started) return fail(DIVANS_GPU_EINVAL, "a stream coded call by call is open on this codec");
@@ -1488,13 +1492,33 @@ extern "C" int divans_gpu_lit_decode_commands_batch(divans_gpu_codec* c, const u
     LitCommandLists cl;
     cl.cmd_begin = d_cmd_begin; cl.cmds = (const LitCommand*)d_cmds; cl.lit_sizes = d_lit_sizes;
     cl.ins = d_ins; cl.ins_offsets = d_ins_offsets; cl.ins_sizes = d_ins_sizes;
+    cl.hist = d_hist; cl.hist_offsets = d_hist_offsets; cl.hist_sizes = d_hist_sizes;
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     ++c->table_launch_seq;
-    lit_decode2_commands_kernel_name(b, c->mix, c->last_decode_kernel, sizeof(c->last_decode_kernel));
+    lit_decode2_commands_kernel_name(b, c->mix, d_hist != nullptr, c->last_decode_kernel, sizeof(c->last_decode_kernel));
     HIP_TRY(launch_decode2_commands(b, cl, c->mix, c->last_decode_grid, c->stream));
     HIP_TRY(hipEventRecord(c->ev[4], c->stream));
     c->timing_pending_dec = true;
     return 0;
+}
+
+extern "C" int divans_gpu_lit_decode_commands_batch(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                                    const uint32_t* d_in_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                                    const divans_lit_command* d_cmds, const uint32_t* d_lit_sizes, uint32_t lit_stream_len,
+                                                    const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                                    uint8_t* d_raw, const uint64_t* d_raw_offsets, const uint32_t* d_raw_sizes) {
+    return decode_commands_impl(c, d_in, d_in_offsets, d_in_sizes, n_streams, d_cmd_begin, d_cmds, d_lit_sizes, lit_stream_len, d_ins, d_ins_offsets,
+                                d_ins_sizes, d_raw, d_raw_offsets, d_raw_sizes, nullptr, nullptr, nullptr);
+}
+
+extern "C" int divans_gpu_lit_decode_commands_history_batch(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                                            const uint32_t* d_in_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                                            const divans_lit_command* d_cmds, const uint32_t* d_lit_sizes, uint32_t lit_stream_len,
+                                                            const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                                            uint8_t* d_raw, const uint64_t* d_raw_offsets, const uint32_t* d_raw_sizes,
+                                                            const uint8_t* d_hist, const uint64_t* d_hist_offsets, const uint32_t* d_hist_sizes) {
+    return decode_commands_impl(c, d_in, d_in_offsets, d_in_sizes, n_streams, d_cmd_begin, d_cmds, d_lit_sizes, lit_stream_len, d_ins, d_ins_offsets,
+                                d_ins_sizes, d_raw, d_raw_offsets, d_raw_sizes, d_hist, d_hist_offsets, d_hist_sizes);
 }
 
 // General streams encoded from their command lists: the kernels of lit_commands.hip derive the literals and the segment
@@ -1502,17 +1526,21 @@ extern "C" int divans_gpu_lit_decode_commands_batch(divans_gpu_codec* c, const u
 // encoders then run on those lists as they do for divans_gpu_lit_encode_segments_batch.  The work arrays are one codec-owned
 // allocation that only grows: round_up(lit_stream_len, 16) + 16 bytes per stream (literal slot, offset, size, segment begin) and 16
 // bytes per command (room for its segment: a stream has one per Literal command with bytes).  Their size needs the number of commands, which only the device knows: the two ends of
-// d_cmd_begin are read back, which waits for the codec's stream once per call.
-extern "C" int divans_gpu_lit_encode_commands_batch(divans_gpu_codec* c, const uint8_t* d_raw, const uint64_t* d_raw_offsets,
-                                                    const uint32_t* d_raw_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
-                                                    const divans_lit_command* d_cmds, uint32_t lit_stream_len,
-                                                    const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
-                                                    uint8_t* d_out, uint64_t out_slot, uint64_t* d_out_offsets, uint32_t* d_out_sizes,
-                                                    uint32_t* d_lit_sizes) {
+// d_cmd_begin are read back, which waits for the codec's stream once per call.  The history triple (all null: none) is that of
+// divans_gpu_lit_encode_commands_history_batch: both entry points are this function.
+static int encode_commands_impl(divans_gpu_codec* c, const uint8_t* d_raw, const uint64_t* d_raw_offsets,
+                                const uint32_t* d_raw_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                const divans_lit_command* d_cmds, uint32_t lit_stream_len,
+                                const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                uint8_t* d_out, uint64_t out_slot, uint64_t* d_out_offsets, uint32_t* d_out_sizes,
+                                uint32_t* d_lit_sizes,
+                                const uint8_t* d_hist, const uint64_t* d_hist_offsets, const uint32_t* d_hist_sizes) {
     if (!c || !d_raw || !d_raw_offsets || !d_raw_sizes || !d_cmd_begin || !d_cmds || !d_out || !d_out_offsets || !d_out_sizes || !d_lit_sizes)
         return fail(DIVANS_GPU_EINVAL, "null argument");
     if ((d_ins == nullptr) != (d_ins_offsets == nullptr) || (d_ins == nullptr) != (d_ins_sizes == nullptr))
         return fail(DIVANS_GPU_EINVAL, "insert bytes, their offsets and their sizes go together");
+    if ((d_hist == nullptr) != (d_hist_offsets == nullptr) || (d_hist == nullptr) != (d_hist_sizes == nullptr))
+        return fail(DIVANS_GPU_EINVAL, "history bytes, their offsets and their sizes go together");
     if (lit_stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "lit_stream_len exceeds the codec's max_stream_len");
     if (c->sp_started || c->sd_started) return fail(DIVANS_GPU_EINVAL, "a stream coded call by call is open on this codec");
     if (int rc = check_out_slot(out_slot, c->max_stream_len)) return rc;      // what encode_batch_impl refuses, before anything is launched
@@ -1536,6 +1564,7 @@ extern "C" int divans_gpu_lit_encode_commands_batch(divans_gpu_codec* c, const u
     p.n_streams = n_streams; p.lit_stream_len = lit_stream_len;
     p.cmd_begin = d_cmd_begin; p.cmds = (const LitCommand*)d_cmds; p.cmd_first = ends[0]; p.cmd_last = ends[1];
     p.ins = d_ins; p.ins_offsets = d_ins_offsets; p.ins_sizes = d_ins_sizes;
+    p.hist = d_hist; p.hist_offsets = d_hist_offsets; p.hist_sizes = d_hist_sizes;
     p.bt_first = c->geom.bt_first; p.n_btypes = c->geom.n_btypes;
     p.segs = (LitSegment*)c->d_cp;
     p.lit_offsets = (uint64_t*)(c->d_cp + sz_segs);
@@ -1550,6 +1579,27 @@ extern "C" int divans_gpu_lit_encode_commands_batch(divans_gpu_codec* c, const u
     c->timing_pending_cp = true;
     return encode_batch_impl(c, p.lit, p.lit_offsets, p.lit_sizes, lit_stream_len, n_streams, d_out, out_slot, d_out_offsets, d_out_sizes,
                              nullptr, 0, p.seg_begin, (const divans_lit_segment*)p.segs);
+}
+
+extern "C" int divans_gpu_lit_encode_commands_batch(divans_gpu_codec* c, const uint8_t* d_raw, const uint64_t* d_raw_offsets,
+                                                    const uint32_t* d_raw_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                                    const divans_lit_command* d_cmds, uint32_t lit_stream_len,
+                                                    const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                                    uint8_t* d_out, uint64_t out_slot, uint64_t* d_out_offsets, uint32_t* d_out_sizes,
+                                                    uint32_t* d_lit_sizes) {
+    return encode_commands_impl(c, d_raw, d_raw_offsets, d_raw_sizes, n_streams, d_cmd_begin, d_cmds, lit_stream_len, d_ins, d_ins_offsets, d_ins_sizes,
+                                d_out, out_slot, d_out_offsets, d_out_sizes, d_lit_sizes, nullptr, nullptr, nullptr);
+}
+
+extern "C" int divans_gpu_lit_encode_commands_history_batch(divans_gpu_codec* c, const uint8_t* d_raw, const uint64_t* d_raw_offsets,
+                                                            const uint32_t* d_raw_sizes, uint32_t n_streams, const uint32_t* d_cmd_begin,
+                                                            const divans_lit_command* d_cmds, uint32_t lit_stream_len,
+                                                            const uint8_t* d_ins, const uint64_t* d_ins_offsets, const uint32_t* d_ins_sizes,
+                                                            uint8_t* d_out, uint64_t out_slot, uint64_t* d_out_offsets, uint32_t* d_out_sizes,
+                                                            uint32_t* d_lit_sizes,
+                                                            const uint8_t* d_hist, const uint64_t* d_hist_offsets, const uint32_t* d_hist_sizes) {
+    return encode_commands_impl(c, d_raw, d_raw_offsets, d_raw_sizes, n_streams, d_cmd_begin, d_cmds, lit_stream_len, d_ins, d_ins_offsets, d_ins_sizes,
+                                d_out, out_slot, d_out_offsets, d_out_sizes, d_lit_sizes, d_hist, d_hist_offsets, d_hist_sizes);
 }
 
 extern "C" int divans_gpu_codec_last_prepare_ms(divans_gpu_codec* c, float* ms) {

@@ -13,11 +13,15 @@
 //      cannot wrap a position), carry the sums from block to block;
 //   2. check every command of the block against the raw size, the bytes produced so far, the insert size, the block-type count and
 //      lit_stream_len BEFORE any byte of the block is read; the first command that fails names the stream's status bit and ends the walk;
-//   3. lanes holding a Literal command with bytes write its segment (last8 = the eight raw bytes in front of it);
+//   3. lanes holding a Literal command with bytes write its segment (last8 = the eight bytes in front of it in history ++ raw);
 //   4. the wave walks the block's contiguous raw range, PIECE bytes per lane and step.  A lane finds the command that covers its piece
 //      in the block's start positions (LDS, binary search); a piece inside one command moves or compares as a whole, one that crosses
 //      command boundaries goes byte by byte with the command index running along.  Literals go to the stream's literal slot, COPY bytes
 //      are compared with raw[p - distance], INSERT bytes with the insert bytes.
+// History (divans_gpu_lit_encode_commands_history_batch): hist_sizes[s] known bytes lie logically in front of raw[0].  A distance may
+// then reach pos + hlen, last8 of a Literal command near the stream's start takes the history's tail, and a COPY piece is compared
+// with history where p - distance < 0: as a whole when it lies wholly there, byte by byte when its source straddles the history's end.
+// History is only read and may lie inside the raw buffer itself (the pieces of one file, each with the bytes in front of it).
 // Segment begins: exact.  lit_commands_count_kernel counts every stream's Literal commands with bytes, lit_commands_scan_kernel turns
 // the counts into seg_begin[0 .. n_streams] (an exclusive sum, saturated at the records the host allocated: one per command), and the
 // prepare kernel writes stream s's segments at segs[seg_begin[s] ..].  (One slot per command with the tail filled with empty
@@ -58,6 +62,11 @@ __device__ __forceinline__ bool cmds_same(const CmdPieces& a, const CmdPieces& b
     cm_u32x4 x, y;
     __builtin_memcpy(&x, a.v, 16); __builtin_memcpy(&y, b.v, 16);
     return ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) == 0u;
+}
+
+// The byte a COPY of distance `arg` repeats at raw position q: (history ++ raw)[q - arg].  The command was checked: arg - q <= hlen.
+__device__ __forceinline__ uint8_t cmds_copy_source(const uint8_t* raw, const uint8_t* hist, uint32_t hlen, uint32_t q, uint32_t arg) {
+    return q >= arg ? raw[q - arg] : hist[hlen - (arg - q)];
 }
 
 // the stream's commands [c0, c1): begins that do not ascend, or that leave what the host read as the batch's ends, give no list
@@ -108,7 +117,10 @@ __global__ __launch_bounds__(1024) void lit_commands_scan_kernel(const LitComman
     }
 }
 
-__global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(const LitCommandPrepare b) {
+// HIST: the streams have history.  A compile-time choice, as in the decoder's CmdCursor: as a branch at run time it cost lists
+// without history 2 % of the prepare step (profiles/r17_command_history_rate.txt); a call without history runs the kernel it ran before.
+template <bool HIST>
+__device__ __forceinline__ void commands_prepare_body(const LitCommandPrepare& b) {
     // per wave: the block's raw start positions (one more: the block's end), kinds, arguments and literal positions
     __shared__ uint32_t s_start[CMDS_THREADS / 64u][CMDS_BLOCK + 1u];
     __shared__ uint32_t s_kind[CMDS_THREADS / 64u][CMDS_BLOCK], s_arg[CMDS_THREADS / 64u][CMDS_BLOCK], s_lit[CMDS_THREADS / 64u][CMDS_BLOCK];
@@ -119,6 +131,8 @@ __global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(cons
     const uint64_t raw_size = b.raw_sizes[s];
     const uint8_t* ins = b.ins ? b.ins + b.ins_offsets[s] : nullptr;
     const uint32_t ins_size = b.ins ? b.ins_sizes[s] : 0u;
+    const uint8_t* hist = HIST && b.hist ? b.hist + b.hist_offsets[s] : nullptr;     // the bytes logically in front of raw[0] (may lie inside b.raw)
+    const uint32_t hlen = HIST && b.hist ? b.hist_sizes[s] : 0u;
     uint8_t* lit = b.lit + (uint64_t)s * b.lit_slot;
     uint32_t c0, c1;
     uint32_t flags = cmds_range(b, s, c0, c1) ? 0u : LIT_STATUS_BAD_COMMAND;
@@ -147,7 +161,7 @@ __global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(cons
             else if (is_lit) {
                 if (c.arg - b.bt_first >= b.n_btypes || lstart + c.len > b.lit_stream_len) verdict = LIT_STATUS_BAD_SEGMENT;
             } else if (c.kind == LIT_CMD_COPY) {
-                if (c.arg == 0u || c.arg > start) verdict = LIT_STATUS_BAD_COMMAND;
+                if (c.arg == 0u || (c.arg > start && (!HIST || c.arg - start > hlen))) verdict = LIT_STATUS_BAD_COMMAND;
             } else if (c.arg > ins_size || c.len > ins_size - c.arg) verdict = LIT_STATUS_BAD_COMMAND;
         }
         if (nseg + (uint32_t)__shfl((int)e_seg, 63, 64) > seg_room) verdict = LIT_STATUS_BAD_COMMAND;     // (uniform)
@@ -160,7 +174,14 @@ __global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(cons
         if (is_seg) {
             uint64_t l8 = 0u;
             if (start >= 8u) __builtin_memcpy(&l8, raw + start - 8u, 8);
-            else for (uint32_t k = 0; k < (uint32_t)start; ++k) l8 |= (uint64_t)raw[k] << (8u * (8u - (uint32_t)start + k));
+            else if (!HIST) for (uint32_t k = 0; k < (uint32_t)start; ++k) l8 |= (uint64_t)raw[k] << (8u * (8u - (uint32_t)start + k));
+            else for (uint32_t k = 0; k < 8u; ++k) {     // byte k of last8 = history ++ raw at start - 8 + k, zero in front of the history
+                const uint32_t t = (uint32_t)start + k;
+                uint32_t v = 0u;
+                if (t >= 8u) v = raw[t - 8u];
+                else if (hlen >= 8u - t) v = hist[hlen - (8u - t)];
+                l8 |= (uint64_t)v << (8u * k);
+            }
             const LitSegment sg = {c.len, c.arg, (uint32_t)l8, (uint32_t)(l8 >> 32)};
             segs[nseg + e_seg - 1u] = sg;
         }
@@ -180,7 +201,11 @@ __global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(cons
                 const uint32_t kind = s_kind[w][j], arg = s_arg[w][j], off = p - st[j];
                 const CmdPieces v = cmds_load_piece(raw + p);
                 if (kind == LIT_CMD_LITERAL) __builtin_memcpy(lit + s_lit[w][j] + off, v.v, CMDS_PIECE);
-                else if (kind == LIT_CMD_COPY) differs |= !cmds_same(v, cmds_load_piece(raw + p - arg));
+                else if (kind == LIT_CMD_COPY) {
+                    if (!HIST || arg <= p) differs |= !cmds_same(v, cmds_load_piece(raw + p - arg));
+                    else if (arg - p >= CMDS_PIECE) differs |= !cmds_same(v, cmds_load_piece(hist + (hlen - (arg - p))));      // wholly history
+                    else for (uint32_t k = 0; k < CMDS_PIECE; ++k) differs |= v.v[k] != cmds_copy_source(raw, hist, hlen, p + k, arg);
+                }
                 else differs |= !cmds_same(v, cmds_load_piece(ins + arg + off));
             } else {
                 const uint32_t n = blk_end - p0 < CMDS_PIECE ? (uint32_t)(blk_end - p0) : CMDS_PIECE;
@@ -190,7 +215,7 @@ __global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(cons
                     const uint32_t kind = s_kind[w][j], arg = s_arg[w][j], off = q - st[j];
                     const uint8_t v = raw[q];
                     if (kind == LIT_CMD_LITERAL) lit[s_lit[w][j] + off] = v;
-                    else if (kind == LIT_CMD_COPY) differs |= v != raw[q - arg];
+                    else if (kind == LIT_CMD_COPY) differs |= v != (HIST ? cmds_copy_source(raw, hist, hlen, q, arg) : raw[q - arg]);
                     else differs |= v != ins[arg + off];
                 }
             }
@@ -212,11 +237,15 @@ __global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(cons
     }
 }
 
+__global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_kernel(const LitCommandPrepare b) { commands_prepare_body<false>(b); }
+__global__ __launch_bounds__(CMDS_THREADS) void lit_commands_prepare_history_kernel(const LitCommandPrepare b) { commands_prepare_body<true>(b); }
+
 hipError_t launch_commands_prepare(const LitCommandPrepare& b, hipStream_t st) {
     const uint32_t per = CMDS_THREADS / 64u;
     hipLaunchKernelGGL(lit_commands_count_kernel, dim3((b.n_streams + per - 1u) / per), dim3(CMDS_THREADS), 0, st, b);
     hipLaunchKernelGGL(lit_commands_scan_kernel, dim3(1), dim3(1024), 0, st, b);
-    hipLaunchKernelGGL(lit_commands_prepare_kernel, dim3((b.n_streams + per - 1u) / per), dim3(CMDS_THREADS), 0, st, b);
+    if (b.hist) hipLaunchKernelGGL(lit_commands_prepare_history_kernel, dim3((b.n_streams + per - 1u) / per), dim3(CMDS_THREADS), 0, st, b);
+    else hipLaunchKernelGGL(lit_commands_prepare_kernel, dim3((b.n_streams + per - 1u) / per), dim3(CMDS_THREADS), 0, st, b);
     return hipGetLastError();
 }
 

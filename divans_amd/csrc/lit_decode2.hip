@@ -451,12 +451,13 @@ __device__ __forceinline__ void init_table2(const Table2& t, const Caches& cc, u
 
 // LIST: how a stream's literals are split into Literal commands -- LIST_NONE: they are not; LIST_SEGS: by a segment list that
 // carries every command's context (b.segs); LIST_CMDS: by the stream's command list (cl), whose Copy and Insert commands this
-// kernel runs into the stream's raw output itself and whose Literal commands take their context from there (CmdCursor).
-constexpr int LIST_NONE = 0, LIST_SEGS = 1, LIST_CMDS = 2;
+// kernel runs into the stream's raw output itself and whose Literal commands take their context from there (CmdCursor);
+// LIST_CMDS_HIST: the same for streams with history bytes in front of their output (cl.hist).
+constexpr int LIST_NONE = 0, LIST_SEGS = 1, LIST_CMDS = 2, LIST_CMDS_HIST = 3;
 
 template <int MM, bool CTXC, bool MIX, int LIST, int CM>
 __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, const LitCommandLists& cl) {
-    constexpr bool SEG = LIST == LIST_SEGS, CMD = LIST == LIST_CMDS;
+    constexpr bool SEG = LIST == LIST_SEGS, CMD = LIST == LIST_CMDS || LIST == LIST_CMDS_HIST;
     const LdsView lv = load_config_to_lds<MM, CTXC>(lds, b);
     const LitGeometry& g = b.geom;
     const int lane = threadIdx.x & 63, li = lane & 15, rbase = lane & 48, rbase4 = rbase << 2, li1 = li + 1;
@@ -504,7 +505,7 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, co
         uint32_t ctab = LIT_BLOB_CTXF;      // context table of the current literal block type
         SegCursor sc;
         if (SEG) sc.start(b, s, seg_last8, ctab);
-        CmdCursor cx;
+        CmdCursor<LIST == LIST_CMDS_HIST> cx;
         if (CMD) cx.start(b, cl, s, li, seg_last8, ctab);     // (runs the commands in front of the first literal)
         hist.set(seg_last8, PERM);
         uint32_t k1 = CTXC ? 0u : lv.ctx[LIT_BLOB_LUT1CLASS + hist.p2];   // lut1 class of the byte before the previous one
@@ -620,6 +621,12 @@ template <int MM, bool CTXC, bool MIX, int CM>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_kernel(const LitBatch b, const LitCommandLists cl) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     decode2_body<MM, CTXC, MIX, LIST_CMDS, CM>(b, lds, cl);
+}
+// ... and the instances for streams with history (divans_gpu_lit_decode_commands_history_batch): a call without history runs the ones above
+template <int MM, bool CTXC, bool MIX, int CM>
+__global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_hist_kernel(const LitBatch b, const LitCommandLists cl) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    decode2_body<MM, CTXC, MIX, LIST_CMDS_HIST, CM>(b, lds, cl);
 }
 
 
@@ -884,17 +891,23 @@ static LitKernel pick_decode2(bool mix, bool seg, uint32_t cm, bool two_way, boo
 typedef void (*LitCmdKernel)(const LitBatch, const LitCommandLists);
 
 template <bool MIX, int CM>
-static LitCmdKernel pick_decode2_cmd_cm(int mm, bool ctxc) {
-    switch ((mm == 4 ? 2 : (mm == 0 ? 1 : 0)) * 2 + (ctxc ? 1 : 0)) {
+static LitCmdKernel pick_decode2_cmd_cm(int mm, bool ctxc, bool hist) {
+    const int which = (mm == 4 ? 2 : (mm == 0 ? 1 : 0)) * 2 + (ctxc ? 1 : 0);
+    if (hist) switch (which) {
+    case 0: return lit_decode2_cmd_hist_kernel<-1, false, MIX, CM>; case 1: return lit_decode2_cmd_hist_kernel<-1, true, MIX, CM>;
+    case 2: return lit_decode2_cmd_hist_kernel<0, false, MIX, CM>;  case 3: return lit_decode2_cmd_hist_kernel<0, true, MIX, CM>;
+    case 4: return lit_decode2_cmd_hist_kernel<4, false, MIX, CM>;  default: return lit_decode2_cmd_hist_kernel<4, true, MIX, CM>;
+    }
+    switch (which) {
     case 0: return lit_decode2_cmd_kernel<-1, false, MIX, CM>; case 1: return lit_decode2_cmd_kernel<-1, true, MIX, CM>;
     case 2: return lit_decode2_cmd_kernel<0, false, MIX, CM>;  case 3: return lit_decode2_cmd_kernel<0, true, MIX, CM>;
     case 4: return lit_decode2_cmd_kernel<4, false, MIX, CM>;  default: return lit_decode2_cmd_kernel<4, true, MIX, CM>;
     }
 }
-// two cache sets: the high rows (2-way), or none
-static LitCmdKernel pick_decode2_cmd(bool mix, bool cached, int mm, bool ctxc) {
-    if (mix) return cached ? pick_decode2_cmd_cm<true, CM_HS | CM_HC | CM_2WAY>(mm, ctxc) : pick_decode2_cmd_cm<true, 0>(mm, ctxc);
-    return cached ? pick_decode2_cmd_cm<false, CM_HS | CM_2WAY>(mm, ctxc) : pick_decode2_cmd_cm<false, 0>(mm, ctxc);
+// two cache sets: the high rows (2-way), or none; with or without history
+static LitCmdKernel pick_decode2_cmd(bool mix, bool cached, int mm, bool ctxc, bool hist) {
+    if (mix) return cached ? pick_decode2_cmd_cm<true, CM_HS | CM_HC | CM_2WAY>(mm, ctxc, hist) : pick_decode2_cmd_cm<true, 0>(mm, ctxc, hist);
+    return cached ? pick_decode2_cmd_cm<false, CM_HS | CM_2WAY>(mm, ctxc, hist) : pick_decode2_cmd_cm<false, 0>(mm, ctxc, hist);
 }
 
 static uint32_t wanted_cache_mask(uint32_t dm_log2) {
@@ -950,10 +963,10 @@ void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap)
              ctxc ? "true" : "false", mix ? "true" : "false", seg ? "true" : "false", cmv);
 }
 
-void lit_decode2_commands_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap) {
+void lit_decode2_commands_kernel_name(const LitBatch& b, bool mix, bool hist, char* buf, size_t cap) {
     const int mm = (b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4) ? b.geom.mm_uniform : -1;
     const int cmv = wanted_cache_mask(b.dm_log2) ? ((mix ? (CM_HS | CM_HC) : CM_HS) | CM_2WAY) : 0;
-    snprintf(buf, cap, "divans_hip::lit_decode2_cmd_kernel<%d, %s, %s, %d>", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false", cmv);
+    snprintf(buf, cap, "divans_hip::lit_decode2_cmd_%skernel<%d, %s, %s, %d>", hist ? "hist_" : "", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false", cmv);
 }
 
 hipError_t launch_decode2_commands(const LitBatch& b, const LitCommandLists& cl, bool mix, uint32_t blocks, hipStream_t st) {
@@ -961,7 +974,7 @@ hipError_t launch_decode2_commands(const LitBatch& b, const LitCommandLists& cl,
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     // the host passes lit_decode2_commands_caches() and the 2-way organisation; the lists come with raw ranges
     if (cm != supported_cache_mask(mix, true, cm) || (cm && !(b.dm_shift >> 31)) || (b.dm_shift & LIT_DM_PINNED) || b.segs || !b.out_offsets || !b.out_sizes) return hipErrorInvalidValue;
-    LitCmdKernel k = pick_decode2_cmd(mix, cm != 0u, mm, b.geom.ctx_const >= 0);
+    LitCmdKernel k = pick_decode2_cmd(mix, cm != 0u, mm, b.geom.ctx_const >= 0, cl.hist != nullptr);
     const uint32_t lds = lit_lds_bytes2(b);
     if (lds > 65536u) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(LIT_THREADS), lds, st, b, cl);

@@ -268,14 +268,20 @@ __device__ __forceinline__ void drain_stores() {
 // literal decoded so far at its place in the output (take()).  All values but `oa` are uniform over the stream's 16 lanes.
 //
 // Every address follows from the command list alone, and every command is checked before it runs: a command that would write
-// past the stream's raw size, read in front of its start or outside its insert bytes, or that names an unknown kind or a block
+// past the stream's raw size, read in front of its history (its start where it has none) or outside its insert bytes, or that names an unknown kind or a block
 // type without a table raises its status bit and ends the walk -- `live` goes false and the stream writes nothing more (the
 // literals that remain are still decoded, under a context that no longer matters, and dropped).
+//
+// HIST: the streams have history (divans_gpu_lit_decode_commands_history_batch).  A compile-time choice: as a branch at run time the
+// history cost lists WITHOUT history 2.2-5.3 % of their decode time (profiles/r17_command_history_rate.txt), so the kernels of a
+// call without history are instantiated without it and are the kernels they were.
+template <bool HIST>
 struct CmdCursor {
     const LitCommand* cmds; uint32_t idx, end, left;
     uint32_t pos, rlen;              // bytes of output produced so far, the stream's raw size
     uint8_t* out;                    // the stream's raw range
     const uint8_t* ins; uint32_t ins_size;
+    const uint8_t* hist; uint32_t hlen;   // history: hist[hlen - 1] is the byte just in front of out[0] (hlen = 0: none)
     uint32_t flags;                  // status bits this stream raised
     bool live;                       // a Literal command is open: the literals being decoded belong at out[pos ..]
     uint32_t oa;                     // per lane: the place in `out` of the literal this lane holds in the byte loop's 16-byte output group
@@ -315,6 +321,25 @@ struct CmdCursor {
             for (uint32_t u = 0; u < 4u; ++u) { const uint64_t j = j0 + 16u * u; if (j < n) dst[j] = v[u]; }
         }
     }
+    // The same for a copy that begins in front of out[0] (d > pos, d - pos <= hlen): source byte k of the d bytes in front of the
+    // command is history while k < d - pos and output from there on, so a source range -- or the period of an overlapping copy --
+    // may straddle the history's end.  Every source byte still lies in front of the command.
+    __device__ __forceinline__ void copy_from_history(uint32_t n, uint32_t d, int li) {
+        uint8_t* dst = out + pos;
+        const uint32_t back = d - pos;                      // source bytes that are history: 1 .. hlen
+        const uint8_t* hsrc = hist + (hlen - back);
+        const bool wraps = d < n;
+        for (uint64_t j0 = (uint64_t)li; j0 < n; j0 += 64u) {
+            uint8_t v[4] = {};
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                const uint64_t j = j0 + 16u * u;
+                if (j < n) { const uint32_t k = wraps ? (uint32_t)j % d : (uint32_t)j; v[u] = k < back ? hsrc[k] : out[k - back]; }
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) { const uint64_t j = j0 + 16u * u; if (j < n) dst[j] = v[u]; }
+        }
+    }
     __device__ __forceinline__ void insert(uint32_t n, uint32_t at, int li) {
         uint8_t* dst = out + pos;
         const uint8_t* src = ins + at;
@@ -322,7 +347,8 @@ struct CmdCursor {
     }
 
     // Runs every command up to the next Literal command with bytes (or to the end of the list), then reads that command's context back:
-    // last8 = the eight bytes in front of it, newest in bits 56..63, zeros in front of the stream's start.
+    // last8 = the eight bytes in front of it in history ++ output, newest in bits 56..63, zeros in front of the history's start.
+    // A stream without history (hlen = 0) never takes the two history branches: they ask for arg > pos, and for hlen != 0 at pos < 8.
     __device__ __forceinline__ void advance(const LitGeometry& g, int li, uint64_t& last8, uint32_t& ctab) {
         live = false;
         while (left == 0u && idx < end) {
@@ -338,9 +364,10 @@ struct CmdCursor {
                 left = c.len;
                 live = true;
             } else if (c.kind == LIT_CMD_COPY) {
-                if (c.arg == 0u || c.arg > pos) { fail(LIT_STATUS_BAD_COMMAND); break; }
+                if (c.arg == 0u || (c.arg > pos && (!HIST || c.arg - pos > hlen))) { fail(LIT_STATUS_BAD_COMMAND); break; }     // (pos + hlen may pass 2^32)
                 drain_stores();          // the bytes it reads: literals, or what the command before it wrote
-                copy(c.len, c.arg, li);
+                if (HIST && c.arg > pos) copy_from_history(c.len, c.arg, li);
+                else copy(c.len, c.arg, li);
                 pos += c.len;
             } else {
                 if (c.arg > ins_size || c.len > ins_size - c.arg) { fail(LIT_STATUS_BAD_COMMAND); break; }
@@ -352,6 +379,7 @@ struct CmdCursor {
         drain_stores();
         int v = 0;
         if (li < 8 && pos >= 8u - (uint32_t)li) v = (int)out[(size_t)pos - 8u + (uint32_t)li];
+        else if (HIST && li < 8 && hlen >= 8u - (uint32_t)li - pos) v = (int)hist[hlen - (8u - (uint32_t)li - pos)];     // pos < 8: the history's tail
         const uint32_t lo = (uint32_t)row_bcast<0>(v) | ((uint32_t)row_bcast<1>(v) << 8) | ((uint32_t)row_bcast<2>(v) << 16) | ((uint32_t)row_bcast<3>(v) << 24);
         const uint32_t hi = (uint32_t)row_bcast<4>(v) | ((uint32_t)row_bcast<5>(v) << 8) | ((uint32_t)row_bcast<6>(v) << 16) | ((uint32_t)row_bcast<7>(v) << 24);
         last8 = ((uint64_t)hi << 32) | lo;
@@ -360,6 +388,7 @@ struct CmdCursor {
         cmds = cl.cmds; idx = cl.cmd_begin[s]; end = cl.cmd_begin[s + 1]; left = 0u;
         pos = 0u; rlen = b.out_sizes[s]; out = b.out + b.out_offsets[s];
         ins = cl.ins ? cl.ins + cl.ins_offsets[s] : nullptr; ins_size = cl.ins ? cl.ins_sizes[s] : 0u;
+        hist = HIST && cl.hist ? cl.hist + cl.hist_offsets[s] : nullptr; hlen = HIST && cl.hist ? cl.hist_sizes[s] : 0u;
         flags = 0u; oa = 0u; gstart = 0u;
         advance(b.geom, li, last8, ctab);
     }

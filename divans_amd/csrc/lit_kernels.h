@@ -94,6 +94,10 @@ struct LitCommandLists {
     const LitCommand* cmds;
     const uint32_t* lit_sizes;  // [n_streams] literal bytes the stream's coded bytes hold
     const uint8_t* ins; const uint64_t* ins_offsets; const uint32_t* ins_sizes;   // insert bytes of every stream, or all null
+    // History (divans_gpu_lit_decode_commands_history_batch), or all null: the hist_sizes[s] bytes at hist + hist_offsets[s] lie logically
+    // in front of stream s's output -- a COPY may reach into them, a Literal command near the stream's start takes its context from
+    // them.  Only read; the ranges of different streams may overlap (a shared dictionary), none may meet a raw range of the launch.
+    const uint8_t* hist; const uint64_t* hist_offsets; const uint32_t* hist_sizes;
 };
 // The step in front of the segment encoders for a batch ENCODED from its commands (lit_commands.hip, launch_commands_prepare): stream
 // s = raw + raw_offsets[s], raw_sizes[s] bytes at any alignment, commands cmds[cmd_begin[s] .. cmd_begin[s + 1]), insert bytes as in
@@ -108,7 +112,8 @@ struct LitCommandPrepare {
     const uint32_t* cmd_begin; const LitCommand* cmds;
     uint32_t cmd_first, cmd_last;   // cmd_begin[0], cmd_begin[n_streams] as the host read them: segs holds cmd_last - cmd_first records
     const uint8_t* ins; const uint64_t* ins_offsets; const uint32_t* ins_sizes;   // or all null
-    uint32_t bt_first, n_btypes;    // the block types a Literal command may name (LitGeometry)
+    const uint8_t* hist; const uint64_t* hist_offsets; const uint32_t* hist_sizes;   // history as in LitCommandLists, or all null; may lie inside `raw`
+    uint32_t bt_first, n_btypes;   // the block types a Literal command may name (LitGeometry)
     uint8_t* lit; uint64_t lit_slot;   // literal slots: lit_stream_len rounded up to 16 bytes each
     uint64_t* lit_offsets; uint32_t* lit_sizes;   // [n_streams]
     uint32_t* seg_begin;            // [n_streams + 1]
@@ -232,7 +237,7 @@ hipError_t launch_decode2(const LitBatch& b, bool mix, uint32_t blocks, hipStrea
 // lit_decode2_kernel with the stream's Copy / Insert commands executed on the device (lit_decode2_cmd_kernel_*): b.dm_log2 = what
 // lit_decode2_commands_caches() leaves, the 2-way organisation whatever b.dm_shift says
 hipError_t launch_decode2_commands(const LitBatch& b, const LitCommandLists& cl, bool mix, uint32_t blocks, hipStream_t st);
-void lit_decode2_commands_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);
+void lit_decode2_commands_kernel_name(const LitBatch& b, bool mix, bool hist, char* buf, size_t cap);   // hist: the lists come with a history (lit_decode2_cmd_hist_kernel)
 uint32_t lit_decode2_commands_caches(uint32_t dm_log2, bool mix, uint32_t total_rows);   // the high-row caches of dm_log2, or none
 void lit_decode_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);    // the instances the two launchers pick, as rocprofv3 spells them
 void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap);

@@ -161,6 +161,31 @@ int divans_gpu_lit_decode_commands_batch(divans_gpu_codec *c,
         const uint32_t *d_lit_sizes, uint32_t lit_stream_len,
         const uint8_t *d_ins, const uint64_t *d_ins_offsets, const uint32_t *d_ins_sizes,
         uint8_t *d_raw, const uint64_t *d_raw_offsets, const uint32_t *d_raw_sizes);
+/* The same call for streams that do not begin at nothing: stream i has h = d_hist_sizes[i] HISTORY bytes H = d_hist + d_hist_offsets[i]
+ * (any alignment) that lie logically in front of its output, H[h - 1] being the byte just before out[0] -- the earlier pieces of a
+ * file that is decoded piece by piece (the reference's ring buffer outlives a metablock, src/cmd_to_raw/mod.rs:69-86), or a
+ * dictionary all streams of the batch share (all offsets equal).  Ranges of different streams may overlap or be identical; history
+ * is only ever read; h == 0 gives the stream of the call above.
+ *   COPY     the distance may be 1 .. pos + h (pos = bytes produced so far by this stream; the sum may exceed 2^32 and does not
+ *            wrap).  The byte for output index q = pos - distance + j comes from out[q] if q >= 0, else from H[h + q].  An
+ *            overlapping copy (distance < len) still repeats the `distance` bytes in front of the command, which may straddle the
+ *            history's end.  A distance of 0 or above pos + h raises DIVANS_GPU_STATUS_BAD_COMMAND, contained as above.
+ *   LITERAL  its context is the eight bytes in front of the command in H ++ out, zeros only in front of the history's start
+ *            (last_8_literals is reloaded from the ring buffer whatever wrote it, src/codec/mod.rs:771-783).
+ * A history range must not intersect any raw output range of the same call: streams run concurrently, the result is unspecified
+ * otherwise (pass the pieces of one file in successive calls, each reading what the earlier calls wrote).  Nothing outside a stream's
+ * own raw range is written, nothing outside its raw, insert, coded and history ranges is read, whatever the commands say.
+ * All three history pointers NULL: this IS the call above -- same bytes, status and flags; any other partial combination returns
+ * DIVANS_GPU_EINVAL.  Same refusals (generation 1 codecs, an open call-by-call stream, lit_stream_len).  A call with the triple
+ * runs kernel instances of its own (lit_decode2_cmd_hist_kernel, what divans_gpu_codec_last_decode_kernel then names): lists without
+ * history cost what they cost through the call above. */
+int divans_gpu_lit_decode_commands_history_batch(divans_gpu_codec *c,
+        const uint8_t *d_in, const uint64_t *d_in_offsets, const uint32_t *d_in_sizes, uint32_t n_streams,
+        const uint32_t *d_cmd_begin, const divans_lit_command *d_cmds,
+        const uint32_t *d_lit_sizes, uint32_t lit_stream_len,
+        const uint8_t *d_ins, const uint64_t *d_ins_offsets, const uint32_t *d_ins_sizes,
+        uint8_t *d_raw, const uint64_t *d_raw_offsets, const uint32_t *d_raw_sizes,
+        const uint8_t *d_hist, const uint64_t *d_hist_offsets, const uint32_t *d_hist_sizes);
 
 /* ---- general streams encoded from their command lists ---------------------------------------------------------------
  * The other direction, with the same inputs: what a compressor has is the raw bytes and the LITERAL / COPY / INSERT list its match
@@ -195,6 +220,21 @@ int divans_gpu_lit_encode_commands_batch(divans_gpu_codec *c,
         const uint8_t *d_ins, const uint64_t *d_ins_offsets, const uint32_t *d_ins_sizes,
         uint8_t *d_out, uint64_t out_slot, uint64_t *d_out_offsets, uint32_t *d_out_sizes,
         uint32_t *d_lit_sizes /* out: literal bytes of stream i, what the decode call is told */);
+/* The same call with a history per stream (d_hist, d_hist_offsets, d_hist_sizes as divans_gpu_lit_decode_commands_history_batch
+ * takes them): a COPY distance may be 1 .. pos + h, a LITERAL command's last8 is taken from H ++ raw.  Here history may lie
+ * anywhere, INSIDE d_raw included -- all pieces of one file go into a single call, each with the bytes in front of it as its
+ * history -- since d_raw and d_hist are only read.  DIVANS_GPU_STATUS_BAD_COMMAND: a distance of 0 or above pos + h, or a COPY whose
+ * bytes differ from H ++ raw at p - distance.
+ *   Status 0 means: divans_gpu_lit_decode_commands_history_batch, given the same lists, the same history, these coded bytes and
+ *   d_lit_sizes, gives the raw bytes back.
+ * All three history pointers NULL: this IS the call above; any other partial combination returns DIVANS_GPU_EINVAL. */
+int divans_gpu_lit_encode_commands_history_batch(divans_gpu_codec *c,
+        const uint8_t *d_raw, const uint64_t *d_raw_offsets, const uint32_t *d_raw_sizes, uint32_t n_streams,
+        const uint32_t *d_cmd_begin, const divans_lit_command *d_cmds, uint32_t lit_stream_len,
+        const uint8_t *d_ins, const uint64_t *d_ins_offsets, const uint32_t *d_ins_sizes,
+        uint8_t *d_out, uint64_t out_slot, uint64_t *d_out_offsets, uint32_t *d_out_sizes,
+        uint32_t *d_lit_sizes,
+        const uint8_t *d_hist, const uint64_t *d_hist_offsets, const uint32_t *d_hist_sizes);
 /* hipEvent time of the prepare step (three small launches: count, scan, prepare) inside the last divans_gpu_lit_encode_commands_batch call (0 before the first); waits for it. */
 int divans_gpu_codec_last_prepare_ms(divans_gpu_codec *c, float *ms);
 
