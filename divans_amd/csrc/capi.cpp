@@ -1671,6 +1671,16 @@ static int placement_step(divans_gpu_codec* c, uint32_t want, uint32_t n_streams
         *measure = true;
         return 0;
     }
+    // A candidate was swapped in and no measurement is in flight: the call that swapped it failed (its launch, or an event record
+    // around it).  The candidate was never measured -- give it back and put the best placement in its place before anything else, or
+    // the swap below would overwrite best_tm, lose the real best and leak its memory.  The failed call may have launched: wait first.
+    // (The state also arises when the hipStreamSynchronize of the measurement block below failed: that candidate was measured but not
+    // yet compared, and is dropped like an unmeasured one -- the search tries its kind again.)
+    if (!ps.pending && ps.best_tm.p) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        table_free(c->tm, false);
+        c->tm = std::move(ps.best_tm); ps.best_tm = TableMem(); c->d_tables = c->tm.p;
+    }
     if (n_streams != ps.sig_streams || stream_len != ps.sig_len) return 0;      // another shape: decoded on the placement in use, not compared
     if (ps.pending) {
         float t = 0.f;

@@ -104,3 +104,59 @@ def build_batch_test(sanitizer="address,undefined"):
     if _newer(exe, objs + [batch_obj, driver]):
         subprocess.run([CXX, "-std=c++17"] + san + ["-o", exe, driver, batch_obj] + objs + ["-I" + os.path.join(ROOT, "include"), "-lpthread"], check=True)
     return exe
+
+
+# ---- the launch contract of the batch C ABI (tests/c/README.md) ------------------------------------------------------------------
+CAPI_SOURCES = ["capi.cpp", "lit_kernels.hip", "lit_decode2.hip", "lit_bucket.hip", "lit_bucket_mix.hip", "lit_bucket_ctx.hip", "lit_commands.hip"]
+
+
+def find_hipcc():
+    """the HIP compiler driver and its clang++, or (None, None): the launch-contract test skips without them"""
+    import shutil
+    for cand in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
+        if cand and os.path.exists(cand):
+            root = os.path.dirname(os.path.dirname(os.path.realpath(cand)))
+            for clang in (os.path.join(root, "lib", "llvm", "bin", "clang++"), os.path.join(root, "llvm", "bin", "clang++")):
+                if os.path.exists(clang):
+                    return cand, clang
+    return None, None
+
+
+def build_capi_contract(csrc=None, tag="contract"):
+    """tests/c/_build/capi_contract: divans_amd/csrc/capi.cpp and the six .hip files compiled for the HOST only (hipcc
+    --offload-host-only: the launchers and kernel stubs, no device code), tests/c/fakehip_rt.cpp in place of libamdhip64 and the
+    driver tests/c/capi_contract.cpp, everything under -fsanitize=address,undefined.  A stand-alone program: nothing is preloaded.
+    `csrc` selects another copy of the product sources (a copy with a deliberate break, to see a contract check fire)."""
+    from concurrent.futures import ThreadPoolExecutor
+    hipcc, clang = find_hipcc()
+    if not hipcc:
+        raise RuntimeError("hipcc not found")
+    csrc = csrc or os.path.join(ROOT, "divans_amd", "csrc")
+    os.makedirs(OUT, exist_ok=True)
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+    flags = ["--offload-arch=gfx950", "--offload-host-only", "-x", "hip", "-std=c++17", "-O1", "-g"] + [f for s in san for f in ("-Xarch_host", s)]
+    headers = [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h")] + [os.path.join(ROOT, "include", "divans_gpu.h"),
+               os.path.join(ROOT, "tests", "c", "fakehip_rt.h"), os.path.abspath(__file__)]
+    jobs = [(os.path.join(csrc, s), os.path.join(OUT, f"{tag}_{s}.o")) for s in CAPI_SOURCES]
+    jobs += [(os.path.join(ROOT, "tests", "c", s), os.path.join(OUT, f"{tag}_{s}.o")) for s in ("fakehip_rt.cpp", "capi_contract.cpp")]
+
+    def compile_one(job):
+        src, obj = job
+        if not os.path.exists(obj) or any(os.path.getmtime(d) > os.path.getmtime(obj) for d in [src] + headers):
+            subprocess.run([hipcc] + flags + ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "c"), "-c", src, "-o", obj], check=True)
+        return obj
+
+    with ThreadPoolExecutor(max_workers=min(len(jobs), 8)) as ex:
+        objs = list(ex.map(compile_one, jobs))
+    # every host-only object refers to the device code it would carry as __hip_fatbin_<hash>: data nobody reads here
+    names = subprocess.run(["nm", "-u"] + objs, check=True, capture_output=True, text=True).stdout.split()
+    fatbins = sorted({n for n in names if n.startswith("__hip_fatbin_")})
+    stub = os.path.join(OUT, tag + "_fatbins.c")
+    text = "".join(f"char {n}[16];\n" for n in fatbins)
+    if not os.path.exists(stub) or open(stub).read() != text:
+        with open(stub, "w") as f:
+            f.write(text)
+    exe = os.path.join(OUT, "capi_contract" if tag == "contract" else "capi_contract_" + tag)
+    if _newer(exe, objs + [stub]):
+        subprocess.run([clang] + san + ["-g", "-o", exe, "-x", "c", stub, "-x", "none"] + objs + ["-lpthread"], check=True)
+    return exe
