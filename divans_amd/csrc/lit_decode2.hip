@@ -592,6 +592,11 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, co
             // to exactly those; anything else means a truncated, corrupt or mismatched stream
             corrupt |= (SA != (1ull << 31)) | (SB != (1ull << 31));
         }
+        // The row requested past the stream's last byte (or for an empty stream) is never used, but its load may still be in flight
+        // and the compiler counts the register as free: without this wait the next stream's address arithmetic can be overwritten
+        // by the late data (tests/test_isa_contracts_cpu.py, contract A).  Once per stream.
+        if (DIVANS_D2_ASYNC && MIX && (CM & (CM_HS | CM_HC))) wait_async(mrowH.st, mrowH.cm);
+        if (DIVANS_D2_ASYNC && !MIX && (CM & CM_HS)) wait_async(rowH.value);
         if (SEG && li == 0) sc.finish();
         if (CMD && li == 0) cx.finish(b, s);
         corrupt |= ww.pos != ww.nwords;     // every coded word consumed, none read past the end
