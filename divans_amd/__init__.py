@@ -622,7 +622,11 @@ class LiteralCodec:
             "divans_gpu_lit_encode_packed")
 
     def set_block_types(self, n_btypes):
-        """Context tables for literal block types 0 .. n_btypes-1 (general streams with BlockSwitchLiteral commands)."""
+        """Context tables for literal block types 0 .. n_btypes-1, 1 <= n_btypes <= 256 (general streams with BlockSwitchLiteral
+        commands).  Above 8 types, where the context map is not constant, the kernels read a second table layout (2304 + 64 n bytes
+        of LDS, two LDS reads per byte for the context): such a codec codes and decodes segment and command lists only -- the calls
+        without lists, `model_batch`, the call-by-call stream calls, `row_replay` and `set_encode_path(2)` raise -- until a later
+        call with n_btypes <= 8 gives the first layout back (include/divans_gpu.h)."""
         _check(self._lib.divans_gpu_codec_set_block_types(self._h, int(n_btypes)), "divans_gpu_codec_set_block_types")
 
     def encode_segments_batch(self, d_in, in_offsets, in_sizes, n_streams, stream_len, seg_begin, segs, outputs):

@@ -266,7 +266,10 @@ extern "C" int divans_gpu_speed_accepted(int32_t inc, int32_t lim) {
 // LIT_BLOB_CTXF[bt][prev][k] among the distinct contexts of `prev`, numbered in order of first appearance over (bt, k < lut1_classes);
 // entries k >= lut1_classes copy class 0 as the context table does.  The table goes behind the mixing mask (no other offset of the
 // blob moves; mix_bt_sort_kernel, lit_bucket_ctx.hip, is its only reader).  Returns the largest number of slots any `prev` takes.
+// A codec with more than LIT_MAX_BTYPES block types has no slot table (its blob is in the wide layout and its encoder has no bucketed
+// pass that would read one): 0 slots where the context map is not constant, the one row a constant context leaves every `prev` otherwise.
 static uint32_t derive_high_row_slots(const LitGeometry& g, std::vector<uint8_t>& blob) {
+    if (g.n_btypes > LIT_MAX_BTYPES) return g.ctx_const >= 0 ? 1u : 0u;
     const size_t at = (size_t)g.mix_off + DIVANS_GPU_NUM_MIXING_VALUES;
     blob.resize(at + (size_t)LIT_CTXF_BYTES * g.n_btypes, 0);
     uint32_t most = 0;
@@ -296,7 +299,10 @@ static uint32_t derive_stride_distance(const divans_lit_config& cfg, const LitGe
     bool ctx_seen[256] = {false};
     for (uint32_t bt = 0; bt < g.n_btypes; ++bt)
         for (uint32_t prev = 0; prev < 256u; ++prev)
-            for (uint32_t k = 0; k < g.lut1_classes; ++k) ctx_seen[blob[LIT_BLOB_CTXF + LIT_CTXF_BYTES * bt + prev * 8u + k]] = true;
+            for (uint32_t k = 0; k < g.lut1_classes; ++k) {
+                if (g.n_btypes > LIT_MAX_BTYPES) ctx_seen[blob[LIT_BLOB_CMAP + LIT_CMAP_BYTES * bt + blob[LIT_BLOB_SEL + prev * 8u + k]]] = true;     // the wide layout
+                else ctx_seen[blob[LIT_BLOB_CTXF + LIT_CTXF_BYTES * bt + prev * 8u + k]] = true;
+            }
     uint32_t dist = 0;
     for (int idx = 0; idx < DIVANS_GPU_NUM_MIXING_VALUES; ++idx) {
         if (!ctx_seen[idx & 0xff]) continue;
@@ -311,8 +317,8 @@ static uint32_t derive_stride_distance(const divans_lit_config& cfg, const LitGe
 // Tables are built for the literal block types [bt_first, bt_first + n_btypes): one for a batch of single-segment
 // streams (cfg.btype), all of 0..max for streams with BlockSwitchLiteral commands between their segments.
 static int derive_geometry(const divans_lit_config& cfg, uint32_t bt_first, uint32_t n_btypes, LitGeometry& g, std::vector<uint8_t>& blob) {
-    if (n_btypes == 0 || n_btypes > LIT_MAX_BTYPES || bt_first + n_btypes > 256u)
-        return fail(DIVANS_GPU_EINVAL, "a codec keeps context tables for 1..8 consecutive literal block types");
+    if (n_btypes == 0 || n_btypes > LIT_WIDE_MAX_BTYPES || bt_first + n_btypes > 256u)
+        return fail(DIVANS_GPU_EINVAL, "a codec keeps context tables for 1..256 consecutive literal block types (no type above 255)");
     if (cfg.prediction_mode > 3) return fail(DIVANS_GPU_EINVAL, "prediction_mode must be 0..3 (codec/interface.rs:252-256)");
     if (cfg.context_mixing >= 15) return fail(DIVANS_GPU_EINVAL, "context_mixing must be < 15 (codec/interface.rs:359)");
     for (int i = 0; i < 4; ++i) {
@@ -320,7 +326,8 @@ static int derive_geometry(const divans_lit_config& cfg, uint32_t bt_first, uint
         if (!divans_gpu_speed_accepted(s.inc, s.lim))
             return fail(DIVANS_GPU_EINVAL, "literal_adaptation speed with a negative increment (divans_gpu_speed_accepted)");
     }
-    const uint32_t mix_off = LIT_BLOB_CTXF + LIT_CTXF_BYTES * n_btypes;
+    const bool wide_blob = n_btypes > LIT_MAX_BTYPES;      // the second layout (lit_kernels.h): SEL[prev][class], then a 64-byte map row per type
+    const uint32_t mix_off = lit_ctx_table_bytes(n_btypes);
     blob.assign(mix_off + DIVANS_GPU_NUM_MIXING_VALUES, 0);
     uint8_t lut0[256], lut1[256];
     make_luts(cfg.prediction_mode, lut0, lut1);
@@ -340,11 +347,13 @@ static int derive_geometry(const divans_lit_config& cfg, uint32_t bt_first, uint
     uint32_t maxctx = 0; int first = -1; bool constant = true;
     for (uint32_t bt = 0; bt < n_btypes; ++bt) {
         const uint8_t* cmap64 = cfg.literal_context_map + 64u * (bt_first + bt);  // literal.rs:114 cmap_index = sel + (btype << 6)
+        if (wide_blob) std::memcpy(&blob[LIT_BLOB_CMAP + LIT_CMAP_BYTES * bt], cmap64, LIT_CMAP_BYTES);
         for (int prev = 0; prev < 256; ++prev) {
             for (int k = 0; k < 8; ++k) {
                 const uint8_t sel = (uint8_t)((lut0[prev] | class_value[k < nclass ? k : 0]) & 63);
                 const uint8_t c = cmap64[sel];
-                blob[LIT_BLOB_CTXF + LIT_CTXF_BYTES * bt + prev * 8 + k] = c;
+                if (wide_blob) blob[LIT_BLOB_SEL + prev * 8 + k] = sel;
+                else blob[LIT_BLOB_CTXF + LIT_CTXF_BYTES * bt + prev * 8 + k] = c;
                 if (k >= nclass) continue;
                 ctx_seen[c] = true;
                 maxctx = std::max<uint32_t>(maxctx, c);
@@ -444,6 +453,14 @@ static LitBatch lit_batch(const divans_gpu_codec* c, uint32_t n_streams, uint32_
 }
 // LitBatch::byte_rank of the decode launches: the learned or hinted order once it is on the device, null = numeric
 static const uint8_t* byte_rank_of(const divans_gpu_codec* c) { return (c->byte_order != 1u && c->rank_ready) ? c->d_rank : nullptr; }
+
+// What a codec in the wide context-table layout (more than LIT_MAX_BTYPES block types, context map not constant) does not do: kernel
+// instances of that layout exist for segment and command lists only
+static int refuse_wide(const divans_gpu_codec* c, const char* what) {
+    if (!lit_wide(c->geom)) return 0;
+    return fail(DIVANS_GPU_EINVAL, std::string(what) + " is not available on a codec with more than 8 literal block types and a context map that is not constant "
+                                   "(divans_gpu_codec_set_block_types: the wide context-table layout serves the segment and command entry points only)");
+}
 
 static uint32_t groups_per_block(const divans_gpu_codec*) { return LIT_THREADS / 16; }
 static bool use_decode2(const divans_gpu_codec* c) { return c->decode_gen == 2u && c->blocks2 != 0u && !c->geom.wrap_check; }
@@ -654,7 +671,7 @@ static int ensure_sf(divans_gpu_codec* c, uint32_t n_streams) {
 // the mixing mask unless the mixing value is one the kernels are specialised for (0 or 4, see effective_mm)
 static uint32_t config_lds_bytes(const LitGeometry& g) {
     const bool mask_in_lds = !(g.mm_uniform == 0 || g.mm_uniform == 4);
-    return (g.ctx_const < 0 ? LIT_BLOB_CTXF + LIT_CTXF_BYTES * g.n_btypes : 0u) + (mask_in_lds ? 8192u : 0u);
+    return (g.ctx_const < 0 ? lit_ctx_table_bytes(g.n_btypes) : 0u) + (mask_in_lds ? 8192u : 0u);
 }
 
 // launch geometry, LDS cache organisation and encoder path that follow from the table geometry
@@ -711,6 +728,9 @@ static void configure_from_geometry(divans_gpu_codec* c) {
     // (derive_high_row_slots); the chain keeps eight high rows per bucket.  A constant context is one bucket per stream for the
     // context model, as above
     if (c->mix && c->geom.mm_uniform == 4 && c->geom.n_btypes > 1u && c->geom.ctx_const < 0 && c->high_row_slots <= 8u && !wrap) c->bucket_pass = PASS_MIX_BT;
+    // the sort kernels of the context-keyed passes read the fused tables: more than LIT_MAX_BTYPES block types under a context map that
+    // is not constant are coded by the streaming kernels (a constant context keeps the pass it has at eight types: no table is read)
+    if (lit_wide(c->geom)) c->bucket_pass = PASS_NONE;
 }
 
 extern "C" void divans_gpu_codec_destroy(divans_gpu_codec* c);
@@ -736,7 +756,7 @@ extern "C" int divans_gpu_codec_create(divans_gpu_codec** out, const divans_lit_
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = (uint32_t)prop.multiProcessorCount;
     configure_from_geometry(c);
-    hipError_t he = hipMalloc(&c->d_blob, LIT_BLOB_MAX_BYTES + LIT_CTXF_BYTES * LIT_MAX_BTYPES);   // + the high-row slot tables
+    hipError_t he = hipMalloc(&c->d_blob, LIT_BLOB_ALLOC_BYTES);   // the fused tables + the high-row slot tables; a wide blob is smaller (lit_kernels.h)
     if (he == hipSuccess) he = hipMalloc(&c->d_status, 64);
     if (he == hipSuccess) he = hipMalloc(&c->d_rank, 256);
     if (he == hipSuccess) he = hipEventCreate(&c->ps.e0);
@@ -887,6 +907,9 @@ extern "C" int divans_gpu_codec_set_block_types(divans_gpu_codec* c, uint32_t n_
 extern "C" int divans_gpu_codec_set_encode_path(divans_gpu_codec* c, uint32_t path) {
     if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
     if (path > 2u) return fail(DIVANS_GPU_EINVAL, "path must be 0 (automatic), 1 (streaming) or 2 (bucketed)");
+    if (path == 2u && lit_wide(c->geom))
+        return fail(DIVANS_GPU_EINVAL, "no bucketed encoder pass exists for more than 8 literal block types under a context map that is not constant (the wide context-table "
+                                       "layout): such a codec codes its lists with the streaming kernels, path 0 or 1");
     if (path == 2u && c->bucket_pass == PASS_NONE)      // (a pass that exists is accepted; whether a call takes it is select_pass)
         return fail(DIVANS_GPU_EINVAL, "the bucketed encoder needs streams of at most 65536 bytes and either one stride distance of 2, 3, 4 or 8 everywhere (mixing values 5, 6, 7, "
                                        "or 8 and above) with a constant context, no mixing and speeds whose row totals stay inside i16, or mixing value 4 everywhere (with no context map and no mixing, or "
@@ -1279,6 +1302,7 @@ static int model_pass(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* 
     b.seg_begin = d_seg_begin; b.segs = (const LitSegment*)d_segs;
     set_cache_fields(c, b);
     if (d_segs && b.cache_mode != 2u && b.cache_mode != 0u) return fail(DIVANS_GPU_EINVAL, "segment lists need the default (high-nibble-row) cache or none");
+    if (!d_segs) { if (int rr = refuse_wide(c, "a batch call without segment lists")) return rr; }
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     ++c->table_launch_seq;
     c->last_encode_path = 1u;
@@ -1344,6 +1368,7 @@ static int encode_batch_impl(divans_gpu_codec* c, const uint8_t* d_in, const uin
                              const uint32_t* d_seg_begin, const divans_lit_segment* d_segs) {
     if (!c || !d_in || !d_out || !d_out_offsets || !d_out_sizes) return fail(DIVANS_GPU_EINVAL, "null argument");
     if ((d_seg_begin == nullptr) != (d_segs == nullptr)) return fail(DIVANS_GPU_EINVAL, "seg_begin and segs go together");
+    if (!d_segs) { if (int rc = refuse_wide(c, "a batch call without segment lists")) return rc; }
     if (n_streams == 0) return 0;
     if (int rc = check_batch_shape(c, d_in_offsets, d_in_sizes, stream_len)) return rc;
     if (int rc = check_out_slot(out_slot, d_in_sizes ? c->max_stream_len : stream_len)) return rc;
@@ -1366,6 +1391,7 @@ extern "C" int divans_gpu_lit_encode_packed(divans_gpu_codec* c, const uint8_t* 
                                             uint32_t stream_len, uint32_t n_streams, uint8_t* d_packed, uint64_t packed_cap,
                                             uint64_t* d_packed_offsets, uint32_t* d_sizes, uint64_t* d_total, uint32_t sub_batch) {
     if (!c || !d_in || !d_packed || !d_packed_offsets || !d_sizes || !d_total) return fail(DIVANS_GPU_EINVAL, "null argument");
+    if (int rc = refuse_wide(c, "a batch call without segment lists")) return rc;
     if (int rc = check_batch_shape(c, d_in_offsets, d_in_sizes, stream_len)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(uint64_t), c->stream));
@@ -1417,6 +1443,7 @@ extern "C" int divans_gpu_lit_encode_segments_batch(divans_gpu_codec* c, const u
 extern "C" int divans_gpu_lit_model_batch(divans_gpu_codec* c, const uint8_t* d_in, const uint64_t* d_in_offsets,
                                           const uint32_t* d_in_sizes, uint32_t stream_len, uint32_t n_streams, uint32_t* d_pairs) {
     if (!c || !d_in || !d_pairs) return fail(DIVANS_GPU_EINVAL, "null argument");
+    if (int rc = refuse_wide(c, "divans_gpu_lit_model_batch")) return rc;
     if (n_streams == 0) return 0;
     if (int rc = check_batch_shape(c, d_in_offsets, d_in_sizes, stream_len)) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -1641,6 +1668,9 @@ static void decode2_shape(divans_gpu_codec* c, uint32_t n_streams, bool segs, Li
         }
         grid = std::min(grid, (n_streams + groups_per_block(c) - 1u) / groups_per_block(c));
     }
+    // wide context tables: the instances that exist are the 2-way ones, so whatever organisation was chosen comes down to it (as the
+    // command calls reduce it)
+    if (lit_wide(c->geom)) b.dm_shift = (b.dm_shift & 0x1f1f1f1fu) | 0x80000000u;
     // The high stride rows of the plain stride-1 decoder: the rows of the most frequent previous bytes stay in LDS for the whole stream
     // instead of competing for tagged sets (a rare byte then evicts nobody: 3.6-8.1 instead of 7.2-12.6 % of a text stream's high
     // rows go to memory, tests/test_pinned_rows_cpu.py).  That presumes an order that ranks by frequency -- the learned one once it is
@@ -1714,6 +1744,7 @@ static int decode_batch_impl(divans_gpu_codec* c, const uint8_t* d_in, const uin
                              const uint64_t* d_out_offsets, const uint32_t* d_out_sizes, uint32_t stream_len,
                              const uint32_t* d_seg_begin, const divans_lit_segment* d_segs) {
     if (!c || !d_in || !d_in_offsets || !d_in_sizes || !d_out) return fail(DIVANS_GPU_EINVAL, "null argument");
+    if (!d_segs) { if (int rc = refuse_wide(c, "a batch call without segment lists")) return rc; }
     if (n_streams == 0) return 0;
     if (int rc = check_batch_shape(c, d_out_offsets, d_out_sizes, stream_len)) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -1722,7 +1753,7 @@ static int decode_batch_impl(divans_gpu_codec* c, const uint8_t* d_in, const uin
     // the first batch -- an earlier encode call's input or this call's output)
     const bool order_settled = !(c->byte_order == 0u && !c->rank_ready && c->geom.mm_uniform == 4);
     const uint32_t want = table_candidates_of(c);
-    const bool qualifies = want > 1u && !c->tables_tuned && 2u * (uint64_t)n_streams >= resident_groups(c) && order_settled &&
+    const bool qualifies = want > 1u && !c->tables_tuned && !lit_wide(c->geom) && 2u * (uint64_t)n_streams >= resident_groups(c) && order_settled &&
                            !c->sp_started && !c->sd_started;      // (a stream coded call by call keeps its state IN the tables)
     const bool eager = c->eager_tune;                   // divans_gpu_codec_tune_tables(c, k >= 2): every placement on this call
     bool measure = false;
@@ -1740,6 +1771,9 @@ static int decode_batch_impl(divans_gpu_codec* c, const uint8_t* d_in, const uin
         b.cache_bytes_per_wg = (LIT_THREADS / 16) * b.cache_rows_high * 34u;
     }
 #endif
+    if (lit_wide(c->geom) && !use_decode2(c)) {       // generation 1 reads the wide layout without a row cache (its one wide instance)
+        b.cache_mode = 0u; b.cache_rows_high = b.cache_rows_low = 0u; b.cache_bytes_per_wg = 0u;
+    }
     if (d_segs && !use_decode2(c) && b.cache_mode != 2u && b.cache_mode != 0u) return fail(DIVANS_GPU_EINVAL, "segment lists need the default (high-nibble-row) cache or none");
 #if DIVANS_WITH_EXPERIMENTAL_DECODERS
     const bool transposed = use_decode_t(c) && !d_segs;      // (segment lists: the first generation's kernel)
@@ -1815,6 +1849,7 @@ extern "C" int divans_gpu_codec_row_replay(divans_gpu_codec* c, const uint8_t* d
     if (!c || !d_literals || !ms) return fail(DIVANS_GPU_EINVAL, "null argument");
     if ((d_offsets == nullptr) != (d_sizes == nullptr)) return fail(DIVANS_GPU_EINVAL, "offsets and sizes go together");
     if (n_streams == 0 || stream_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "bad batch shape");
+    if (int rc = refuse_wide(c, "divans_gpu_codec_row_replay")) return rc;
     if (!use_decode2(c) || c->geom.mm_uniform != 4) return fail(DIVANS_GPU_EINVAL, "row replay exists for the stride-1 configurations of the second-generation decoder");
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_tables(c); if (rc) return rc;
@@ -2137,6 +2172,7 @@ static int stream_rans(divans_gpu_codec* c, uint32_t n_chunks, uint32_t syms_las
 
 extern "C" int divans_gpu_lit_stream_begin(divans_gpu_codec* c) {
     if (!c) return fail(DIVANS_GPU_EINVAL, "null codec");
+    if (int rc = refuse_wide(c, "coding a stream call by call")) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (!c->d_wstate && hipMalloc(&c->d_wstate, 64) != hipSuccess) return fail(DIVANS_GPU_ENOMEM, "hipMalloc(stream state) failed");
     c->sp_pending = 0; c->sp_started = false;
@@ -2149,6 +2185,7 @@ extern "C" int divans_gpu_lit_stream_begin(divans_gpu_codec* c) {
 extern "C" int divans_gpu_lit_stream_encode(divans_gpu_codec* c, const uint8_t* in, uint32_t len, uint64_t last8, uint8_t* out, size_t out_cap,
                                             uint32_t* chunk_sizes, uint32_t max_chunks, uint32_t* n_chunks, size_t* out_len) {
     if (!c || !in || !out || !n_chunks || !out_len || !c->d_wstate) return fail(DIVANS_GPU_EINVAL, "bad argument (divans_gpu_lit_stream_begin first)");
+    if (int rc = refuse_wide(c, "coding a stream call by call")) return rc;
     if (len == 0 || len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "a piece is 1 .. max_stream_len bytes");
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_tables(c); if (rc) return rc;
@@ -2202,6 +2239,7 @@ extern "C" int divans_gpu_lit_stream_decode_begin(divans_gpu_codec* c) {
 extern "C" int divans_gpu_lit_stream_decode(divans_gpu_codec* c, const uint8_t* coded, size_t coded_bytes, uint32_t out_len, uint64_t last8,
                                             uint8_t* out, size_t* consumed_bytes) {
     if (!c || !coded || !out || !consumed_bytes || !c->d_wstate) return fail(DIVANS_GPU_EINVAL, "bad argument (divans_gpu_lit_stream_decode_begin first)");
+    if (int rc = refuse_wide(c, "coding a stream call by call")) return rc;
     if (out_len == 0 || out_len > c->max_stream_len) return fail(DIVANS_GPU_EINVAL, "a call decodes 1 .. max_stream_len bytes");
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_tables(c); if (rc) return rc;

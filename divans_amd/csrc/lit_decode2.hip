@@ -455,10 +455,13 @@ __device__ __forceinline__ void init_table2(const Table2& t, const Caches& cc, u
 // LIST_CMDS_HIST: the same for streams with history bytes in front of their output (cl.hist).
 constexpr int LIST_NONE = 0, LIST_SEGS = 1, LIST_CMDS = 2, LIST_CMDS_HIST = 3;
 
-template <int MM, bool CTXC, bool MIX, int LIST, int CM>
+// WIDE: the context tables are in the second layout (more than LIT_MAX_BTYPES block types, lit_kernels.h) -- with a list and a context map
+// that is not constant only.
+template <int MM, bool CTXC, bool MIX, int LIST, int CM, bool WIDE = false>
 __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, const LitCommandLists& cl) {
     constexpr bool SEG = LIST == LIST_SEGS, CMD = LIST == LIST_CMDS || LIST == LIST_CMDS_HIST;
-    const LdsView lv = load_config_to_lds<MM, CTXC>(lds, b);
+    static_assert(!WIDE || (!CTXC && LIST != LIST_NONE), "the wide layout: segment or command lists over a context map that is not constant");
+    const LdsView lv = load_config_to_lds<MM, CTXC, WIDE>(lds, b);
     const LitGeometry& g = b.geom;
     const int lane = threadIdx.x & 63, li = lane & 15, rbase = lane & 48, rbase4 = rbase << 2, li1 = li + 1;
     const uint32_t gg = blockIdx.x * (LIT_THREADS / 16) + (threadIdx.x >> 4);
@@ -502,17 +505,17 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, co
         History<NEED8> hist;
         hist.perm_off = perm_off;
         uint64_t seg_last8 = 0;
-        uint32_t ctab = LIT_BLOB_CTXF;      // context table of the current literal block type
+        uint32_t ctab = WIDE ? LIT_BLOB_CMAP : LIT_BLOB_CTXF;      // context table of the current literal block type
         SegCursor sc;
-        if (SEG) sc.start(b, s, seg_last8, ctab);
-        CmdCursor<LIST == LIST_CMDS_HIST> cx;
+        if (SEG) sc.start<WIDE>(b, s, seg_last8, ctab);
+        CmdCursor<LIST == LIST_CMDS_HIST, WIDE> cx;
         if (CMD) cx.start(b, cl, s, li, seg_last8, ctab);     // (runs the commands in front of the first literal)
         hist.set(seg_last8, PERM);
         uint32_t k1 = CTXC ? 0u : lv.ctx[LIT_BLOB_LUT1CLASS + hist.p2];   // lut1 class of the byte before the previous one
         uint64_t SA = 0, SB = 0;      // state_a decodes high nibbles, state_b low nibbles (two symbols per byte)
         bool corrupt = false;
         int pad = li;
-        uint32_t ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, hist.p1, k1);
+        uint32_t ctx_cur = context_of<CTXC, WIDE>(g, lv.ctx, ctab, hist.p1, k1);
         Fetched2 rowH = {};
         MixRows mrowH = {};
         if (!MIX) rowH = fetch2<true, MM, NEED8, CM>(g, lv, tb, cc, ctx_cur, hist, 0u);
@@ -545,13 +548,13 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, co
                         const uint32_t byte = (hi << 4) | lo;
                         hist.push(byte, PERM);
                         if (SEG) {   // the next Literal command starts from the ring buffer's last 8 bytes and its own block type
-                            if (--sc.left == 0u) { seg_last8 = hist.last8; sc.advance(g, seg_last8, ctab); hist.set(seg_last8, PERM); }
+                            if (--sc.left == 0u) { seg_last8 = hist.last8; sc.advance<WIDE>(g, seg_last8, ctab); hist.set(seg_last8, PERM); }
                         }
                         if (CMD) {   // the Literal command ends: its bytes go to their places, the commands behind it run, the next one's context is read back
                             if (cx.take(byte, k, li, outb)) { cx.advance(g, li, seg_last8, ctab); if (cx.live) hist.set(seg_last8, PERM); }
                         }
                         if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + hist.p2];
-                        ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, hist.p1, k1);
+                        ctx_cur = context_of<CTXC, WIDE>(g, lv.ctx, ctab, hist.p1, k1);
                         mrowH = fetch_mix2<true, MM, NEED8, CM>(g, lv, tb, cc, ctx_cur, hist, 0u);   // next byte's rows (harmless past the end)
                         finish_mix2<false, CM>(g, tb, cc, li1, rbase4, ml, mrowL, mlo, SB, fl, pl);
                         wp.update(li, fh, ph, fl, pl);
@@ -575,10 +578,10 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, co
                         const uint32_t lo = (uint32_t)sl.sym;
                         const uint32_t byte = (hi << 4) | lo;
                         hist.push(byte, PERM);
-                        if (SEG) { if (--sc.left == 0u) { seg_last8 = hist.last8; sc.advance(g, seg_last8, ctab); hist.set(seg_last8, PERM); } }
+                        if (SEG) { if (--sc.left == 0u) { seg_last8 = hist.last8; sc.advance<WIDE>(g, seg_last8, ctab); hist.set(seg_last8, PERM); } }
                         if (CMD) { if (cx.take(byte, k, li, outb)) { cx.advance(g, li, seg_last8, ctab); if (cx.live) hist.set(seg_last8, PERM); } }
                         if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + hist.p2];
-                        ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, hist.p1, k1);
+                        ctx_cur = context_of<CTXC, WIDE>(g, lv.ctx, ctab, hist.p1, k1);
                         rowH = fetch2<true, MM, NEED8, CM>(g, lv, tb, cc, ctx_cur, hist, 0u);   // next byte's row (harmless past the end)
                         finish2<(CM & CM_LS) != 0>(tb, cc.ls, li1, rbase4, rowL.ref, rowL.value, rowL.is_default, cvl, sl, slot_b, SB, g.inc0, g.lim0);
                         pad_valu<DIVANS_D2_PAD_VALU>(pad);
@@ -632,6 +635,27 @@ template <int MM, bool CTXC, bool MIX, int CM>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_hist_kernel(const LitBatch b, const LitCommandLists cl) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     decode2_body<MM, CTXC, MIX, LIST_CMDS_HIST, CM>(b, lds, cl);
+}
+// The instances of the wide context-table layout: overloads with one trailing template argument (WIDE = 1), so that every instance
+// above keeps its name and its code and these are spelt `...<4, false, true, true, 19, 1>`.  The segment-list ones are `_any` kernels
+// for every mixing value: held to 72 VGPRs they would spill.
+template <int MM, bool CTXC, bool MIX, bool SEG, int CM, int WIDE>
+__global__ __launch_bounds__(LIT_THREADS) void lit_decode2_kernel_any(const LitBatch b) {
+    static_assert(WIDE == 1 && SEG, "the wide instances take segment lists");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    decode2_body<MM, CTXC, MIX, LIST_SEGS, CM, true>(b, lds, LitCommandLists{});
+}
+template <int MM, bool CTXC, bool MIX, int CM, int WIDE>
+__global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_kernel(const LitBatch b, const LitCommandLists cl) {
+    static_assert(WIDE == 1, "the trailing argument only names the wide layout");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    decode2_body<MM, CTXC, MIX, LIST_CMDS, CM, true>(b, lds, cl);
+}
+template <int MM, bool CTXC, bool MIX, int CM, int WIDE>
+__global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_hist_kernel(const LitBatch b, const LitCommandLists cl) {
+    static_assert(WIDE == 1, "the trailing argument only names the wide layout");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    decode2_body<MM, CTXC, MIX, LIST_CMDS_HIST, CM, true>(b, lds, cl);
 }
 
 
@@ -909,8 +933,22 @@ static LitCmdKernel pick_decode2_cmd_cm(int mm, bool ctxc, bool hist) {
     case 4: return lit_decode2_cmd_kernel<4, false, MIX, CM>;  default: return lit_decode2_cmd_kernel<4, true, MIX, CM>;
     }
 }
+// the wide layout: a context map that is not constant
+template <bool MIX, int CM>
+static LitCmdKernel pick_decode2_cmd_wide(int mm, bool hist) {
+    if (hist) return mm == 4 ? lit_decode2_cmd_hist_kernel<4, false, MIX, CM, 1> : (mm == 0 ? lit_decode2_cmd_hist_kernel<0, false, MIX, CM, 1> : lit_decode2_cmd_hist_kernel<-1, false, MIX, CM, 1>);
+    return mm == 4 ? lit_decode2_cmd_kernel<4, false, MIX, CM, 1> : (mm == 0 ? lit_decode2_cmd_kernel<0, false, MIX, CM, 1> : lit_decode2_cmd_kernel<-1, false, MIX, CM, 1>);
+}
+template <bool MIX, int CM>
+static LitKernel pick_decode2_wide(int mm) {
+    return mm == 4 ? lit_decode2_kernel_any<4, false, MIX, true, CM, 1> : (mm == 0 ? lit_decode2_kernel_any<0, false, MIX, true, CM, 1> : lit_decode2_kernel_any<-1, false, MIX, true, CM, 1>);
+}
 // two cache sets: the high rows (2-way), or none; with or without history
-static LitCmdKernel pick_decode2_cmd(bool mix, bool cached, int mm, bool ctxc, bool hist) {
+static LitCmdKernel pick_decode2_cmd(bool mix, bool cached, int mm, bool ctxc, bool hist, bool wide) {
+    if (wide) {
+        if (mix) return cached ? pick_decode2_cmd_wide<true, CM_HS | CM_HC | CM_2WAY>(mm, hist) : pick_decode2_cmd_wide<true, 0>(mm, hist);
+        return cached ? pick_decode2_cmd_wide<false, CM_HS | CM_2WAY>(mm, hist) : pick_decode2_cmd_wide<false, 0>(mm, hist);
+    }
     if (mix) return cached ? pick_decode2_cmd_cm<true, CM_HS | CM_HC | CM_2WAY>(mm, ctxc, hist) : pick_decode2_cmd_cm<true, 0>(mm, ctxc, hist);
     return cached ? pick_decode2_cmd_cm<false, CM_HS | CM_2WAY>(mm, ctxc, hist) : pick_decode2_cmd_cm<false, 0>(mm, ctxc, hist);
 }
@@ -936,7 +974,7 @@ uint32_t lit_decode2_commands_caches(uint32_t dm_log2, bool mix, uint32_t total_
 
 uint32_t lit_lds_bytes2(const LitBatch& b) {
     uint32_t bytes = b.cache_bytes_per_wg;
-    if (b.geom.ctx_const < 0) bytes += LIT_BLOB_CTXF + LIT_CTXF_BYTES * b.geom.n_btypes;
+    if (b.geom.ctx_const < 0) bytes += lit_ctx_table_bytes(b.geom.n_btypes);
     if (!(b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4)) bytes += 8192u;
     if (DIVANS_D2_PERM && b.geom.mm_uniform == 4) bytes += 256u;   // the byte ranks
     return bytes;
@@ -961,6 +999,11 @@ void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap)
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     const int w2 = (b.dm_shift >> 31) ? CM_2WAY : 0;
     int cmv;
+    if (lit_wide(b.geom)) {      // segment lists, the 2-way organisation whatever was asked for, an `_any` kernel for every mixing value
+        cmv = cm ? ((mix ? (CM_HS | CM_HC) : CM_HS) | CM_2WAY) : 0;
+        snprintf(buf, cap, "divans_hip::lit_decode2_kernel_any<%d, false, %s, true, %d, 1>", mm, mix ? "true" : "false", cmv);
+        return;
+    }
     if (b.dm_shift & LIT_DM_PINNED) cmv = CM_HS | CM_PIN;
     else if (mix) cmv = (!seg && cm == (uint32_t)(CM_HS | CM_HC | CM_LC)) ? (CM_HS | CM_HC | CM_LC | w2) : (cm ? (CM_HS | CM_HC | w2) : 0);
     else cmv = (!seg && cm == (uint32_t)(CM_HS | CM_LS)) ? (CM_HS | CM_LS | w2) : (cm ? (CM_HS | w2) : 0);
@@ -971,7 +1014,8 @@ void lit_decode2_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap)
 void lit_decode2_commands_kernel_name(const LitBatch& b, bool mix, bool hist, char* buf, size_t cap) {
     const int mm = (b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4) ? b.geom.mm_uniform : -1;
     const int cmv = wanted_cache_mask(b.dm_log2) ? ((mix ? (CM_HS | CM_HC) : CM_HS) | CM_2WAY) : 0;
-    snprintf(buf, cap, "divans_hip::lit_decode2_cmd_%skernel<%d, %s, %s, %d>", hist ? "hist_" : "", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false", cmv);
+    snprintf(buf, cap, "divans_hip::lit_decode2_cmd_%skernel<%d, %s, %s, %d%s>", hist ? "hist_" : "", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false", cmv,
+             lit_wide(b.geom) ? ", 1" : "");
 }
 
 hipError_t launch_decode2_commands(const LitBatch& b, const LitCommandLists& cl, bool mix, uint32_t blocks, hipStream_t st) {
@@ -979,7 +1023,7 @@ hipError_t launch_decode2_commands(const LitBatch& b, const LitCommandLists& cl,
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     // the host passes lit_decode2_commands_caches() and the 2-way organisation; the lists come with raw ranges
     if (cm != supported_cache_mask(mix, true, cm) || (cm && !(b.dm_shift >> 31)) || (b.dm_shift & LIT_DM_PINNED) || b.segs || !b.out_offsets || !b.out_sizes) return hipErrorInvalidValue;
-    LitCmdKernel k = pick_decode2_cmd(mix, cm != 0u, mm, b.geom.ctx_const >= 0, cl.hist != nullptr);
+    LitCmdKernel k = pick_decode2_cmd(mix, cm != 0u, mm, b.geom.ctx_const >= 0, cl.hist != nullptr, lit_wide(b.geom));
     const uint32_t lds = lit_lds_bytes2(b);
     if (lds > 65536u) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(LIT_THREADS), lds, st, b, cl);
@@ -990,7 +1034,12 @@ hipError_t launch_decode2(const LitBatch& b, bool mix, uint32_t blocks, hipStrea
     const int mm = (b.geom.mm_uniform == 0 || b.geom.mm_uniform == 4) ? b.geom.mm_uniform : -1;
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     if (cm != supported_cache_mask(mix, b.segs != nullptr, cm)) return hipErrorInvalidValue;   // the host passes lit_decode2_effective_caches()
-    LitKernel k = pick_decode2(mix, b.segs != nullptr, cm, (b.dm_shift >> 31) != 0u, (b.dm_shift & LIT_DM_PINNED) != 0u, mm, b.geom.ctx_const >= 0);
+    LitKernel k = nullptr;
+    if (lit_wide(b.geom)) {     // wide context tables: segment lists, the high-row caches in the 2-way organisation or none (the host passes both)
+        if (!b.segs || (cm && !(b.dm_shift >> 31)) || (b.dm_shift & LIT_DM_PINNED)) return hipErrorInvalidValue;
+        if (mix) k = cm ? pick_decode2_wide<true, CM_HS | CM_HC | CM_2WAY>(mm) : pick_decode2_wide<true, 0>(mm);
+        else k = cm ? pick_decode2_wide<false, CM_HS | CM_2WAY>(mm) : pick_decode2_wide<false, 0>(mm);
+    } else k = pick_decode2(mix, b.segs != nullptr, cm, (b.dm_shift >> 31) != 0u, (b.dm_shift & LIT_DM_PINNED) != 0u, mm, b.geom.ctx_const >= 0);
     if (!k) return hipErrorInvalidValue;      // the host asks lit_decode2_can_pin() first
     const uint32_t lds = lit_lds_bytes2(b);
     if (lds > 65536u) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1010,7 +1059,7 @@ hipError_t launch_learn_byte_rank(const uint8_t* data, const uint64_t* offsets, 
 // the instances the benchmark configurations use: constant context without mixing (high-row cache, 2-way or direct mapped),
 // context table with mixing (high stride + FirstNibble caches)
 hipError_t launch_row_replay(const LitBatch& b, bool mix, uint32_t blocks, hipStream_t st) {
-    if (b.geom.mm_uniform != 4 || b.segs) return hipErrorInvalidValue;
+    if (b.geom.mm_uniform != 4 || b.segs || lit_wide(b.geom)) return hipErrorInvalidValue;
     const uint32_t cm = wanted_cache_mask(b.dm_log2);
     const bool two_way = (b.dm_shift >> 31) != 0u, ctxc = b.geom.ctx_const >= 0;
     LitKernel k = nullptr;

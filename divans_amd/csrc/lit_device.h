@@ -190,14 +190,14 @@ __device__ __forceinline__ RowSel select_rows(const LitGeometry& g, const uint8_
 // LDS layout of a workgroup: [16 x row cache (data, then tags)] [context tables unless CTXC] [mixing_mask if MM < 0]
 struct LdsView { uint8_t* base; const uint8_t* ctx; const uint8_t* mix; };
 
-template <int MM, bool CTXC>
+template <int MM, bool CTXC, bool WIDE = false>
 __device__ __forceinline__ LdsView load_config_to_lds(uint8_t* lds, const LitBatch& b) {
     LdsView v;
     v.base = lds;
     uint8_t* p = lds + b.cache_bytes_per_wg;
     v.ctx = p;
     if (!CTXC) {
-        const uint32_t ctx_bytes = LIT_BLOB_CTXF + LIT_CTXF_BYTES * b.geom.n_btypes;
+        const uint32_t ctx_bytes = WIDE ? LIT_BLOB_CMAP + LIT_CMAP_BYTES * b.geom.n_btypes : LIT_BLOB_CTXF + LIT_CTXF_BYTES * b.geom.n_btypes;
         const uint32_t* src = (const uint32_t*)(b.blob + LIT_BLOB_LUT1CLASS);
         for (uint32_t i = threadIdx.x; i < ctx_bytes / 4; i += blockDim.x) ((uint32_t*)p)[i] = src[i];
         p += ctx_bytes;
@@ -215,9 +215,12 @@ __device__ __forceinline__ LdsView load_config_to_lds(uint8_t* lds, const LitBat
 // LIT_BLOB_CTXF[block type][prev][lut1 class of prev_prev]; `ctab` = byte offset of the current block type's table,
 // `k1` (that class) is carried over from the previous byte.  Where LitGeometry::hs_classes lays the high-nibble stride table out by
 // class, the row slot of (prev, class) comes along in bits 8.. (the host put it into the table's free half; select_rows takes the pair apart).
-template <bool CTXC>
+// WIDE (more than LIT_MAX_BTYPES block types, lit_kernels.h): `ctab` = byte offset of the current type's 64-byte context-map row, and the
+// context is CMAP[t][SEL[prev][k1]] -- a second LDS read that depends on the first (hs_classes is 0 there: it needs one block type).
+template <bool CTXC, bool WIDE = false>
 __device__ __forceinline__ uint32_t context_of(const LitGeometry& g, const uint8_t* lds_ctx, uint32_t ctab, uint32_t prev, uint32_t k1) {
     if (CTXC) return (uint32_t)g.ctx_const;
+    if (WIDE) return lds_ctx[ctab + lds_ctx[LIT_BLOB_SEL + (prev << 3) + k1]];
     const uint32_t at = ctab + (prev << 3) + k1;
     uint32_t v = lds_ctx[at];
     if (g.hs_classes) v |= (uint32_t)lds_ctx[at + 4u] << 8;
@@ -228,6 +231,7 @@ __device__ __forceinline__ uint32_t context_of(const LitGeometry& g, const uint8
 // segment still to code; advance() is called when it reaches zero and installs the next segment's context.
 struct SegCursor {
     const LitSegment* segs; uint32_t idx, end, left; uint32_t* status;
+    template <bool WIDE = false>
     __device__ __forceinline__ void advance(const LitGeometry& g, uint64_t& last8, uint32_t& ctab) {
         while (left == 0u && idx < end) {
             const u32x4 sg = *(const u32x4*)(segs + idx);
@@ -239,12 +243,13 @@ struct SegCursor {
                 t = g.n_btypes - 1u;     // inside the tables, but say so -- the stream would be coded under the wrong context map
                 if (status) atomicOr(status, LIT_STATUS_BAD_SEGMENT);
             }
-            ctab = LIT_BLOB_CTXF + t * LIT_CTXF_BYTES;
+            ctab = WIDE ? LIT_BLOB_CMAP + t * LIT_CMAP_BYTES : LIT_BLOB_CTXF + t * LIT_CTXF_BYTES;
         }
     }
+    template <bool WIDE = false>
     __device__ __forceinline__ void start(const LitBatch& b, uint32_t s, uint64_t& last8, uint32_t& ctab) {
         segs = b.segs; idx = b.seg_begin[s]; end = b.seg_begin[s + 1]; left = 0u; status = b.status;
-        advance(b.geom, last8, ctab);
+        advance<WIDE>(b.geom, last8, ctab);
     }
     // After the stream's last byte, by one lane: the lengths have to add up to the stream.  A list that ends early leaves `left`
     // wrapped below zero, one that goes on has bytes or segments over (trailing empty segments are consumed by advance() and
@@ -275,7 +280,7 @@ __device__ __forceinline__ void drain_stores() {
 // HIST: the streams have history (divans_gpu_lit_decode_commands_history_batch).  A compile-time choice: as a branch at run time the
 // history cost lists WITHOUT history 2.2-5.3 % of their decode time (profiles/r17_command_history_rate.txt), so the kernels of a
 // call without history are instantiated without it and are the kernels they were.
-template <bool HIST>
+template <bool HIST, bool WIDE = false>
 struct CmdCursor {
     const LitCommand* cmds; uint32_t idx, end, left;
     uint32_t pos, rlen;              // bytes of output produced so far, the stream's raw size
@@ -360,7 +365,7 @@ struct CmdCursor {
             if (c.kind == LIT_CMD_LITERAL) {
                 const uint32_t t = c.arg - g.bt_first;
                 if (t >= g.n_btypes) { fail(LIT_STATUS_BAD_SEGMENT); break; }
-                ctab = LIT_BLOB_CTXF + t * LIT_CTXF_BYTES;
+                ctab = WIDE ? LIT_BLOB_CMAP + t * LIT_CMAP_BYTES : LIT_BLOB_CTXF + t * LIT_CTXF_BYTES;
                 left = c.len;
                 live = true;
             } else if (c.kind == LIT_CMD_COPY) {

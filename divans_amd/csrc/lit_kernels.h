@@ -13,9 +13,29 @@ constexpr int RANS_THREADS = 64;    // one wave, one lane per stream
 constexpr uint32_t LIT_BLOB_LUT1CLASS = 0;  // class (<8) of literal_lut1[b]: index of its value among the distinct lut1 values
 constexpr uint32_t LIT_BLOB_CTXF = 256;     // [block type][prev][class]: literal_context_map[(lut0[prev] | lut1 value) + 64*btype], literal.rs:97-115
 constexpr uint32_t LIT_CTXF_BYTES = 2048;   // one block type's table; n_btypes of them follow each other
-constexpr uint32_t LIT_MAX_BTYPES = 8;      // block types one codec keeps context tables for (LDS: 2 KB each)
+constexpr uint32_t LIT_MAX_BTYPES = 8;      // block types one codec keeps FUSED context tables for (LDS: 2 KB each)
 // then mixing_mask[8192] at LitGeometry::mix_off = 256 + 2048 * n_btypes
 constexpr uint32_t LIT_BLOB_MAX_BYTES = 256 + LIT_CTXF_BYTES * LIT_MAX_BTYPES + 8192;
+// The second ("wide") layout, for n_btypes > LIT_MAX_BTYPES (up to LIT_WIDE_MAX_BTYPES): lut0 | lut1 is fused once, the context map stays
+// a 64-byte row per block type, and the context of a byte is CMAP[t][SEL[prev][k]] -- two dependent LDS byte reads instead of one.
+//   [0, 256)           lut1 class of a byte (LIT_BLOB_LUT1CLASS, as above)
+//   [256, 2304)        SEL[prev][k] = (lut0[prev] | class_value[k]) & 63; k >= lut1_classes copies class 0, as the fused table does
+//   [2304, 2304 + 64n) CMAP[t][sel] = literal_context_map[64 * (bt_first + t) + sel], t < n = n_btypes
+//   then mixing_mask[8192] at LitGeometry::mix_off = 2304 + 64 n         (26 880 bytes at 256 types: below LIT_BLOB_ALLOC_BYTES)
+// The blob of a codec with more than LIT_MAX_BTYPES types is laid out this way whatever its context map; the KERNELS read it -- the
+// WIDE template argument of the streaming kernels -- only where the map is not constant (lit_wide): under a constant context no
+// kernel reads a context table, and such a codec keeps the instances it has at eight types.
+constexpr uint32_t LIT_BLOB_SEL = 256;
+constexpr uint32_t LIT_BLOB_CMAP = LIT_BLOB_SEL + 2048;
+constexpr uint32_t LIT_CMAP_BYTES = 64;
+constexpr uint32_t LIT_WIDE_MAX_BTYPES = 256;
+// what a codec allocates for its blob: the largest fused blob with the high-row slot tables behind it (capi.cpp derive_high_row_slots)
+constexpr uint32_t LIT_BLOB_ALLOC_BYTES = LIT_BLOB_MAX_BYTES + LIT_CTXF_BYTES * LIT_MAX_BTYPES;
+static_assert(LIT_BLOB_CMAP + LIT_CMAP_BYTES * LIT_WIDE_MAX_BTYPES + 8192 <= LIT_BLOB_ALLOC_BYTES, "the largest wide blob fits the codec's allocation");
+// bytes of the configuration blob in front of the mixing mask (LitGeometry::mix_off) for n block types
+constexpr uint32_t lit_ctx_table_bytes(uint32_t n_btypes) {
+    return n_btypes > LIT_MAX_BTYPES ? LIT_BLOB_CMAP + LIT_CMAP_BYTES * n_btypes : LIT_BLOB_CTXF + LIT_CTXF_BYTES * n_btypes;
+}
 
 // How the (3 x 256 x 256) prior cube of LiteralNibblePriors (codec/priors.rs:35-37) is compacted for
 // one configuration: only the planes / context columns the configuration can reach are materialised.
@@ -37,6 +57,9 @@ struct LitGeometry {
     uint32_t wrap_check;           // some speed lets a row total leave i16 (divans_gpu_speed_supported is false): streaming kernels without
                                    // row caches, which keep such a row recognisable and report a stream that codes with one (lit_kernels.hip blend_row)
 };
+
+// The kernels of a launch read the wide layout (no field says so: it follows from the geometry, and is a template argument on the device)
+inline bool lit_wide(const LitGeometry& g) { return g.n_btypes > LIT_MAX_BTYPES && g.ctx_const < 0; }
 
 // One Literal command of a general stream (codec/mod.rs:711-792): `len` literal bytes coded with the literal block type
 // `btype` (BlockSwitchLiteral, codec/interface.rs:289-292) after last_8_literals has been reloaded from the ring buffer

@@ -268,102 +268,24 @@ __device__ __forceinline__ uint32_t model_finish(const LitGeometry& g, const Tab
     return packed;
 }
 
+// The kernel's text is lit_model_encode_body.h: the wide context-table layout (WIDE, lit_kernels.h) has instances of its own below.
+// The two body files (this one and lit_decode_body.h) use these names of the scope they are included into: the template parameters
+// MM, CTXC, MIX, CACHE, SEG, the kernel argument `b`, `lds` and `constexpr bool WIDE`; they refuse to be included anywhere else.
+#define DIVANS_LIT_KERNEL_BODY 1
 template <int MM, bool CTXC, bool MIX, int CACHE, bool SEG>
 __global__ __launch_bounds__(LIT_THREADS) void lit_model_encode_kernel(const LitBatch b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const LdsView lv = load_config_to_lds<MM, CTXC>(lds, b);
-    const LitGeometry& g = b.geom;
-    const int lane = threadIdx.x & 63, li = lane & 15, rbase = lane & 48;
-    const uint32_t gg = blockIdx.x * (LIT_THREADS / 16) + (threadIdx.x >> 4);
-    const uint32_t G = gridDim.x * (LIT_THREADS / 16);
-    const Table<CACHE> tb = make_table<CACHE>(b, lds, li);
-    for (uint32_t s = gg; s < b.n_streams; s += G) {
-        const uint8_t* in = b.in + (b.in_offsets ? b.in_offsets[s] : (uint64_t)s * b.stream_len);
-        const uint32_t len = b.in_sizes ? b.in_sizes[s] : b.stream_len;
-        uint32_t* sf = b.sf + (size_t)s * 2u * b.max_stream_len;
-        if (!b.resume) init_table(tb, g.total_rows, li);
-        WeightsPair wp; wp.init();
-        if (MIX && b.resume) { const int32_t* p = b.wstate + (li < 8 ? 0 : 3); wp.w.w0 = p[0]; wp.w.w1 = p[1]; wp.w.norm = p[2]; }
-        int nh = wp.norm_high(), nl = wp.norm_low();     // normalized_weight of model_weights[1] (high nibble) / [0] (low nibble)
-        uint64_t last8 = 0;
-        uint32_t ctab = LIT_BLOB_CTXF;      // context table of the current literal block type
-        SegCursor sc;
-        if (SEG) sc.start(b, s, last8, ctab);
-        uint32_t k1 = CTXC ? 0u : lv.ctx[LIT_BLOB_LUT1CLASS + (uint32_t)((last8 >> 48) & 0xffu)];   // lut1 class of prev_prev
-        // each lane holds one literal byte of the current and of the next 16-byte window (coalesced reads)
-        uint32_t mine = ((uint32_t)li < len) ? in[li] : 0u;
-        uint32_t nxt = (16u + li < len) ? in[16u + li] : 0u;
-        // Non-mixing path: every symbol is known, so each row is requested one nibble ahead (right after the previous
-        // row of the SAME table has been stored) and the model math of one nibble runs under the fetch of the next.
-        uint32_t cur = (uint32_t)row_gather((int)mine, rbase, 0);
-        uint32_t ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, (uint32_t)(last8 >> 56), k1);
-        FetchedRow rowH = {}, rowL = {};
-        if (!MIX) {
-            rowH = fetch_row<true, MM, CACHE>(g, lv, tb, ctx_cur, last8, 0u);
-            rowL = fetch_row<false, MM, CACHE>(g, lv, tb, ctx_cur, last8, cur >> 4);
-        }
-        for (uint32_t base = 0; base < len; base += 16) {
-            const uint32_t cnt = len - base < 16u ? len - base : 16u;
-            uint32_t pend_a = 0, pend_b = 0;  // lane k keeps the two pairs of byte base+k
-            for (uint32_t k = 0; k < cnt; ++k) {
-                if (MIX) {
-                    const uint32_t byte = (uint32_t)row_gather((int)mine, rbase, (int)k);
-                    const uint32_t prev = (uint32_t)(last8 >> 56);
-                    const uint32_t ctx = context_of<CTXC>(g, lv.ctx, ctab, prev, k1);
-                    if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + prev];
-                    const uint32_t hi = byte >> 4, lo = byte & 15u;
-                    uint32_t fh = 0, fl = 0;
-                    const uint32_t ph = model_nibble<true, MM, MIX, CACHE>(g, lv, tb, li, rbase, ctx, last8, 0u, (int)hi, nh, fh);
-                    const uint32_t pl = model_nibble<false, MM, MIX, CACHE>(g, lv, tb, li, rbase, ctx, last8, hi, (int)lo, nl, fl);
-                    wp.update(li, fh, ph >> 16, fl, pl >> 16);
-                    nh = wp.norm_high(); nl = wp.norm_low();
-                    last8 = (last8 >> 8) | ((uint64_t)byte << 56);
-                    if (SEG) {   // the next Literal command starts from the ring buffer's last 8 bytes and its own block type
-                        if (--sc.left == 0u) {
-                            sc.advance(g, last8, ctab);
-                            if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + (uint32_t)((last8 >> 48) & 0xffu)];
-                        }
-                    }
-                    pend_a = (uint32_t)li == k ? ph : pend_a;
-                    pend_b = (uint32_t)li == k ? pl : pend_b;
-                } else {
-                    const uint32_t byte = cur;
-                    const uint32_t nb = (uint32_t)row_gather((int)(k + 1u < 16u ? mine : nxt), rbase, (int)((k + 1u) & 15u));
-                    const uint32_t ph = model_finish<CACHE>(g, tb, li, rbase, rowH, (int)(byte >> 4));
-                    last8 = (last8 >> 8) | ((uint64_t)byte << 56);
-                    if (SEG) { if (--sc.left == 0u) sc.advance(g, last8, ctab); }
-                    if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + (uint32_t)((last8 >> 48) & 0xffu)];
-                    ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, (uint32_t)(last8 >> 56), k1);
-                    rowH = fetch_row<true, MM, CACHE>(g, lv, tb, ctx_cur, last8, 0u);           // next byte's high row
-                    const uint32_t pl = model_finish<CACHE>(g, tb, li, rbase, rowL, (int)(byte & 15u));
-                    rowL = fetch_row<false, MM, CACHE>(g, lv, tb, ctx_cur, last8, nb >> 4);     // next byte's low row
-                    cur = nb;
-                    pend_a = (uint32_t)li == k ? ph : pend_a;
-                    pend_b = (uint32_t)li == k ? pl : pend_b;
-                }
-            }
-            // nibble index of byte (base+li) is 2*(base+li): each lane stores its two pairs (8 B; 128 B coalesced per row)
-            if ((uint32_t)li < cnt) {
-                u32x2 v = {pend_a, pend_b};   // written once, read once by the rANS kernel: keep it out of the L2's way
-                __builtin_nontemporal_store(v, (u32x2*)(sf + 2u * (size_t)(base + li)));
-            }
-            mine = nxt;
-            nxt = (base + 32u + li < len) ? in[base + 32u + li] : 0u;
-        }
-        if (SEG && li == 0) sc.finish();
-        if (MIX && b.wstate && (li & 7) == 0) {   // lanes 0 and 8 of the row hold the two Weights objects
-            int32_t* p = b.wstate + (li ? 3 : 0);
-            p[0] = wp.w.w0; p[1] = wp.w.w1; p[2] = wp.w.norm;
-        }
-        if (g.wrap_check) {     // a speed under which a row total can leave i16: say so if one did and was coded with again
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0);
-            if (wrap_scan<CACHE>(g, tb, li, rbase) && li == 0) {
-                if (b.status) atomicOr(b.status, LIT_STATUS_BAD_MODEL);
-                if (b.stream_bad) b.stream_bad[s] = 1;
-            }
-        }
-    }
+    constexpr bool WIDE = false;
+#include "lit_model_encode_body.h"
+}
+// The instances of the wide context-table layout: an overload with one trailing template argument (WIDE = 1), so that every instance
+// above keeps its name and these are spelt `lit_model_encode_kernel<4, false, false, 2, true, 1>`
+template <int MM, bool CTXC, bool MIX, int CACHE, bool SEG, int LAYOUT>
+__global__ __launch_bounds__(LIT_THREADS) void lit_model_encode_kernel(const LitBatch b) {
+    static_assert(LAYOUT == 1, "the trailing argument only names the wide layout");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    constexpr bool WIDE = true;
+#include "lit_model_encode_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -719,111 +641,18 @@ __device__ __forceinline__ void finish_nibble(const LitGeometry& g, const Table<
 template <int MM, bool CTXC, bool MIX, int CACHE, bool SEG>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode_kernel(const LitBatch b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const LdsView lv = load_config_to_lds<MM, CTXC>(lds, b);
-    const LitGeometry& g = b.geom;
-    const int lane = threadIdx.x & 63, li = lane & 15, rbase = lane & 48;
-    const uint32_t gg = blockIdx.x * (LIT_THREADS / 16) + (threadIdx.x >> 4);
-    const uint32_t G = gridDim.x * (LIT_THREADS / 16);
-    const Table<CACHE> tb = make_table<CACHE>(b, lds, li);
-    for (uint32_t s = gg; s < b.n_streams; s += G) {
-        const uint32_t len = b.out_sizes ? b.out_sizes[s] : b.stream_len;
-        uint8_t* out = b.out + (b.out_offsets ? b.out_offsets[s] : (uint64_t)s * b.stream_len);
-        WordWindow ww;
-        ww.in = (const uint32_t*)(b.in + b.in_offsets[s]);
-        ww.nwords = b.in_sizes[s] >> 2;
-        ww.start(li);
-        if (!b.resume) init_table(tb, g.total_rows, li);
-        WeightsPair wp; wp.init();
-        if (MIX && b.resume) { const int32_t* p = b.wstate + (li < 8 ? 0 : 3); wp.w.w0 = p[0]; wp.w.w1 = p[1]; wp.w.norm = p[2]; }
-        int nh = wp.norm_high(), nl = wp.norm_low();     // normalized_weight of model_weights[1] (high nibble) / [0] (low nibble)
-        uint64_t last8 = 0;
-        uint32_t ctab = LIT_BLOB_CTXF;      // context table of the current literal block type
-        SegCursor sc;
-        if (SEG) sc.start(b, s, last8, ctab);
-        uint32_t k1 = CTXC ? 0u : lv.ctx[LIT_BLOB_LUT1CLASS + (uint32_t)((last8 >> 48) & 0xffu)];
-        uint64_t SA = 0, SB = 0;      // state_a decodes high nibbles, state_b low nibbles (two symbols per byte)
-        bool corrupt = false;
-        uint32_t ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, (uint32_t)(last8 >> 56), k1);
-        FetchedRow rowH = {};
-        if (!MIX) rowH = fetch_row<true, MM, CACHE>(g, lv, tb, ctx_cur, last8, 0u);
-        for (uint32_t cbeg = 0; cbeg < len; cbeg += 32768u) {
-            // start of a 65 536-symbol chunk: 16 bytes = state_a, state_b (ans.rs:174-186)
-            {
-                uint32_t a0 = ww.next(li, rbase), a1 = ww.next(li, rbase), b0 = ww.next(li, rbase), b1 = ww.next(li, rbase);
-                SA = ((uint64_t)a1 << 32) | a0;
-                SB = ((uint64_t)b1 << 32) | b0;
-            }
-            const uint32_t cend = cbeg + 32768u < len ? cbeg + 32768u : len;
-            for (uint32_t base = cbeg; base < cend; base += 16u) {
-                const uint32_t cnt = cend - base < 16u ? cend - base : 16u;
-                uint32_t outb = 0;
-                for (uint32_t k = 0; k < cnt; ++k) {
-                    if (MIX) {
-                        const uint32_t prev = (uint32_t)(last8 >> 56);
-                        const uint32_t ctx = context_of<CTXC>(g, lv.ctx, ctab, prev, k1);
-                        if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + prev];
-                        // a state that dropped below 2^31 takes 4 more bytes right before it is used again (ans.rs:432-440)
-                        if (SA < (1ull << 31)) SA = (SA << 32) | ww.next(li, rbase);
-                        uint32_t fh = 0, fl = 0, ph = 0, pl = 0;
-                        const uint32_t hi = decode_nibble<true, MM, MIX, CACHE>(g, lv, tb, li, rbase, ctx, last8, 0u, SA, nh, fh, ph);
-                        if (SB < (1ull << 31)) SB = (SB << 32) | ww.next(li, rbase);
-                        const uint32_t lo = decode_nibble<false, MM, MIX, CACHE>(g, lv, tb, li, rbase, ctx, last8, hi, SB, nl, fl, pl);
-                        wp.update(li, fh, ph, fl, pl);
-                        nh = wp.norm_high(); nl = wp.norm_low();
-                        const uint32_t byte = (hi << 4) | lo;
-                        last8 = (last8 >> 8) | ((uint64_t)byte << 56);
-                        if (SEG) {
-                            if (--sc.left == 0u) {
-                                sc.advance(g, last8, ctab);
-                                if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + (uint32_t)((last8 >> 48) & 0xffu)];
-                            }
-                        }
-                        outb = (uint32_t)li == k ? byte : outb;
-                    } else {
-                        // rowH (this byte's high-nibble row) was requested while the previous byte was being finished
-                        if (SA < (1ull << 31)) SA = (SA << 32) | ww.next(li, rbase);
-                        const int cvh = rowH.is_default ? 4 * (li + 1) : rowH.value;
-                        const uint32_t hi = (uint32_t)search_symbol(cvh, (uint32_t)SA & 0x7fffu, rbase);
-                        const FetchedRow rowL = fetch_row<false, MM, CACHE>(g, lv, tb, ctx_cur, last8, hi);
-                        finish_nibble<CACHE>(g, tb, li, rbase, rowH, cvh, (int)hi, SA);
-                        if (SB < (1ull << 31)) SB = (SB << 32) | ww.next(li, rbase);
-                        const int cvl = rowL.is_default ? 4 * (li + 1) : rowL.value;
-                        const uint32_t lo = (uint32_t)search_symbol(cvl, (uint32_t)SB & 0x7fffu, rbase);
-                        const uint32_t byte = (hi << 4) | lo;
-                        last8 = (last8 >> 8) | ((uint64_t)byte << 56);
-                        if (SEG) { if (--sc.left == 0u) sc.advance(g, last8, ctab); }
-                        if (!CTXC) k1 = lv.ctx[LIT_BLOB_LUT1CLASS + (uint32_t)((last8 >> 48) & 0xffu)];
-                        ctx_cur = context_of<CTXC>(g, lv.ctx, ctab, (uint32_t)(last8 >> 56), k1);
-                        rowH = fetch_row<true, MM, CACHE>(g, lv, tb, ctx_cur, last8, 0u);   // next byte's row (harmless past the end)
-                        finish_nibble<CACHE>(g, tb, li, rbase, rowL, cvl, (int)lo, SB);
-                        outb = (uint32_t)li == k ? byte : outb;
-                    }
-                }
-                if ((uint32_t)li < cnt) __builtin_nontemporal_store((uint8_t)outb, out + base + li);
-            }
-            // rANS is an exact inverse: a chunk that was coded from the start states 2^31 (ans.rs:135-136,331-378) decodes back
-            // to exactly those; anything else means a truncated, corrupt or mismatched stream (the reference would stall on
-            // NeedsMoreInput or fail its checksum)
-            corrupt |= (SA != (1ull << 31)) | (SB != (1ull << 31));
-        }
-        if (SEG && li == 0) sc.finish();
-        if (b.consumed) { corrupt |= ww.pos > ww.nwords; if (li == 0) b.consumed[s] = ww.pos; }
-        else corrupt |= ww.pos != ww.nwords;     // every coded word consumed, none read past the end
-        if (MIX && b.wstate && (li & 7) == 0) {   // lanes 0 and 8 of the row hold the two Weights objects
-            int32_t* p = b.wstate + (li ? 3 : 0);
-            p[0] = wp.w.w0; p[1] = wp.w.w1; p[2] = wp.w.norm;
-        }
-        if (g.wrap_check) {     // the encoder of this stream coded with a row whose i16 total had wrapped: whatever it wrote, it is not these bytes
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0);
-            corrupt |= wrap_scan<CACHE>(g, tb, li, rbase);
-        }
-        if (corrupt && li == 0) {
-            if (b.status) atomicOr(b.status, LIT_STATUS_BAD_STREAM);
-            if (b.stream_bad) b.stream_bad[s] = 1;
-        }
-    }
+    constexpr bool WIDE = false;
+#include "lit_decode_body.h"
 }
+// ... and its wide instances (as lit_model_encode_kernel's)
+template <int MM, bool CTXC, bool MIX, int CACHE, bool SEG, int LAYOUT>
+__global__ __launch_bounds__(LIT_THREADS) void lit_decode_kernel(const LitBatch b) {
+    static_assert(LAYOUT == 1, "the trailing argument only names the wide layout");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    constexpr bool WIDE = true;
+#include "lit_decode_body.h"
+}
+#undef DIVANS_LIT_KERNEL_BODY
 
 // ---------------------------------------------------------------------------------------------
 // pack_streams: exclusive scan of the 4-byte-rounded sizes (single block, 3 phases) + coalesced copy
@@ -1021,12 +850,24 @@ static LitKernel pick_mode_lit_decode_kernel(int cache_mode, bool seg, int mm, b
 }
 #endif
 
+// The wide context-table layout (a context map that is not constant, segment lists): the encoder without a cache or with the
+// high-nibble-row cache, generation 1's decoder without a cache (the wrap-checked launch)
+template <int CACHE>
+static LitKernel pick_wide_model_encode(int mm, bool mix) {
+    if (mix) return mm == 4 ? lit_model_encode_kernel<4, false, true, CACHE, true, 1> : (mm == 0 ? lit_model_encode_kernel<0, false, true, CACHE, true, 1> : lit_model_encode_kernel<-1, false, true, CACHE, true, 1>);
+    return mm == 4 ? lit_model_encode_kernel<4, false, false, CACHE, true, 1> : (mm == 0 ? lit_model_encode_kernel<0, false, false, CACHE, true, 1> : lit_model_encode_kernel<-1, false, false, CACHE, true, 1>);
+}
+static LitKernel pick_wide_decode(int mm, bool mix) {
+    if (mix) return mm == 4 ? lit_decode_kernel<4, false, true, 0, true, 1> : (mm == 0 ? lit_decode_kernel<0, false, true, 0, true, 1> : lit_decode_kernel<-1, false, true, 0, true, 1>);
+    return mm == 4 ? lit_decode_kernel<4, false, false, 0, true, 1> : (mm == 0 ? lit_decode_kernel<0, false, false, 0, true, 1> : lit_decode_kernel<-1, false, false, 0, true, 1>);
+}
+
 // specialisation that will actually run: only 0 and 4 have dedicated MM instances
 static int effective_mm(int mm) { return (mm == 0 || mm == 4) ? mm : -1; }
 
 uint32_t lit_lds_bytes(const LitBatch& b) {
     uint32_t bytes = b.cache_bytes_per_wg;
-    if (b.geom.ctx_const < 0) bytes += LIT_BLOB_CTXF + LIT_CTXF_BYTES * b.geom.n_btypes;
+    if (b.geom.ctx_const < 0) bytes += lit_ctx_table_bytes(b.geom.n_btypes);
     if (effective_mm(b.geom.mm_uniform) < 0) bytes += 8192u;
     return bytes;
 }
@@ -1035,7 +876,11 @@ hipError_t launch_model_encode(const LitBatch& b_in, bool mix, uint32_t blocks, 
     const LitBatch& b = b_in;
     const int mm = effective_mm(b.geom.mm_uniform);
     if (b.segs && b.cache_mode != 2u && b.cache_mode != 0u) return hipErrorInvalidValue;
-    LitKernel k = pick_mode_lit_model_encode_kernel((int)b.cache_mode, b.segs != nullptr, mm, b.geom.ctx_const >= 0, mix);
+    LitKernel k;
+    if (lit_wide(b.geom)) {
+        if (!b.segs) return hipErrorInvalidValue;      // the host refuses list-free calls on such a codec
+        k = b.cache_mode == 2u ? pick_wide_model_encode<2>(mm, mix) : pick_wide_model_encode<0>(mm, mix);
+    } else k = pick_mode_lit_model_encode_kernel((int)b.cache_mode, b.segs != nullptr, mm, b.geom.ctx_const >= 0, mix);
     const uint32_t lds = lit_lds_bytes(b);
     if (lds > 65536u) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(LIT_THREADS), lds, st, b);
@@ -1062,15 +907,17 @@ void lit_decode_kernel_name(const LitBatch& b, bool mix, char* buf, size_t cap) 
     const int mm = effective_mm(b.geom.mm_uniform);
     const bool seg = b.segs != nullptr;
     const int cache = seg ? (b.cache_mode == 2u ? 2 : 0) : (b.cache_mode >= 1u && b.cache_mode <= 3u ? (int)b.cache_mode : 0);
-    snprintf(buf, cap, "divans_hip::lit_decode_kernel<%d, %s, %s, %d, %s>", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false", cache,
-             seg ? "true" : "false");
+    snprintf(buf, cap, "divans_hip::lit_decode_kernel<%d, %s, %s, %d, %s%s>", mm, b.geom.ctx_const >= 0 ? "true" : "false", mix ? "true" : "false", cache,
+             seg ? "true" : "false", lit_wide(b.geom) ? ", 1" : "");
 }
 hipError_t launch_decode(const LitBatch& b_in, bool mix, uint32_t blocks, hipStream_t st) {
     const LitBatch& b = b_in;
     const int mm = effective_mm(b.geom.mm_uniform);
     if (b.segs && b.cache_mode != 2u && b.cache_mode != 0u) return hipErrorInvalidValue;
-    LitKernel k = pick_mode_lit_decode_kernel((int)b.cache_mode, b.segs != nullptr, mm, b.geom.ctx_const >= 0, mix);
-    if (!k) return hipErrorInvalidValue;     // a cache organisation this build holds no generation-1 decoder for
+    LitKernel k;
+    if (lit_wide(b.geom)) k = (b.segs && b.cache_mode == 0u) ? pick_wide_decode(mm, mix) : nullptr;     // the host passes cache mode 0
+    else k = pick_mode_lit_decode_kernel((int)b.cache_mode, b.segs != nullptr, mm, b.geom.ctx_const >= 0, mix);
+    if (!k) return hipErrorInvalidValue;    // a cache organisation this build holds no generation-1 decoder for
     const uint32_t lds = lit_lds_bytes(b);
     if (lds > 65536u) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(LIT_THREADS), lds, st, b);

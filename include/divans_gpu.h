@@ -106,9 +106,20 @@ typedef struct divans_lit_segment {
     uint32_t btype;    /* literal block type in force (< the count given to divans_gpu_codec_set_block_types) */
     uint64_t last8;    /* the 8 output bytes before the command, oldest in bits 0..7, newest in bits 56..63 */
 } divans_lit_segment;
-/* context tables for literal block types 0 .. n_btypes-1 (1..8) instead of the single divans_lit_config::btype.  A grid / cache
- * organisation / decoder generation chosen before with the tuning calls below is kept (clamped to what the LDS holds next to
- * the extra tables).  A segment naming a block type >= n_btypes raises DIVANS_GPU_STATUS_BAD_SEGMENT in the status word. */
+/* context tables for literal block types 0 .. n_btypes-1 (1..256: every type a BlockSwitchLiteral command can name) instead of the
+ * single divans_lit_config::btype.  A grid / cache organisation / decoder generation chosen before with the tuning calls below is
+ * kept (clamped to what the LDS holds next to the extra tables).  A segment naming a block type >= n_btypes raises
+ * DIVANS_GPU_STATUS_BAD_SEGMENT in the status word.
+ * Up to 8 types every type has a fused 2 KB table in LDS (256 + 2048 n bytes per workgroup).  Above 8 types, where the context map
+ * is not constant, the kernels read a second layout: lut0 | lut1 fused once (2 KB) and the context map's 64-byte row per type,
+ * 2304 + 64 n bytes per workgroup (18 688 at 256 types, where eight fused tables take 16 640) and two dependent LDS reads per byte
+ * instead of one.  Such a codec serves the segment and command entry points only: it has no bucketed encoder pass
+ * (divans_gpu_codec_set_encode_path(c, 2) is refused, path 0 codes lists with the streaming kernels; divans_gpu_codec_high_row_slots
+ * reports 0), it takes no part in the table-placement search, a direct-mapped cache organisation comes down to the 2-way one, and the
+ * batch calls without lists, divans_gpu_lit_model_batch, the call-by-call divans_gpu_lit_stream_* calls and
+ * divans_gpu_codec_row_replay return DIVANS_GPU_EINVAL on it.  Under a constant context map no kernel reads a context table: such a
+ * codec keeps its kernels, its bucketed pass and every entry point at any number of types.  A later call with n_btypes <= 8 gives
+ * back the fused layout and everything that goes with it. */
 int divans_gpu_codec_set_block_types(divans_gpu_codec *c, uint32_t n_btypes);
 /* As divans_gpu_lit_encode_batch / _decode_batch; stream i's literal bytes (in command order, concatenated) are split
  * by the segments d_segs[d_seg_begin[i] .. d_seg_begin[i+1]) (device arrays; d_seg_begin has n_streams + 1 entries).
