@@ -2,7 +2,8 @@
 // --offload-host-only) driven on tests/c/fakehip_rt.cpp.  Every launch is checked against the launch contract there; this program
 // makes the calls, scripts times and failures, and asserts what only the sequence shows (placements alive, the pool, clean ends).
 //   capi_contract <scenario> <configs file> <trace file> [<sizes file>]
-// scenarios: small | m6 | placement | pool | failures.  The configs file is written by tests/test_capi_launch_contract_cpu.py from
+// scenarios: small | m6 | placement | pool | failures (codecs on the null stream) | streams_small | streams_placement | streams_host
+// (codecs on a non-blocking stream of the driver's).  The configs file is written by tests/test_capi_launch_contract_cpu.py from
 // the table of tests/test_gpu_encode_dispatch.py: records of {char name[32]; u32 types (~0: as created); u32 path_2_before_types;
 // u32 btype; u32 reserved; divans_lit_config}.  A failed expectation prints EXPECTATION FAILED and exits 2; a contract violation aborts.
 #include <hip/hip_runtime_api.h>
@@ -107,9 +108,11 @@ static Batch make_batch(const std::vector<uint32_t>& sizes, uint32_t msl, uint32
     return b;
 }
 
+// the stream every codec of the run is created on: null in scenarios 1-5, a non-blocking stream of the driver's in the streams_* ones
+static hipStream_t g_stream = nullptr;
 static divans_gpu_codec* make_codec(const Config& cf, uint32_t msl) {
     divans_gpu_codec* c = nullptr;
-    const int rc = divans_gpu_codec_create(&c, &cf.cfg, 0, nullptr, msl);
+    const int rc = divans_gpu_codec_create(&c, &cf.cfg, 0, g_stream, msl);
     EXPECT(rc == 0 && c, "codec_create: %d %s", rc, divans_gpu_last_error());
     return c;
 }
@@ -642,8 +645,294 @@ static void scenario_failures() {
     clean_end();
 }
 
+// ---- scenarios 6-8: the same ABI on a caller's NON-BLOCKING stream (tests/c/README.md, "The stream model") --------------------------
+// On such a stream nothing the library enqueues is complete, as far as the host can see, until the library (or the driver) waits:
+// the destination of every device-to-host copy keeps its old bytes until then, and a synchronous copy, a free or a map that meets
+// an entry still in flight is an `order` / `lifetime` violation.  The effects below stand for the kernels whose results the host
+// reads back; what they write depends on the driver's call counter, so a value left over from an earlier call is a wrong value.
+static uint32_t g_call = 0;                                   // bumped by the driver in front of every call whose results it checks
+static uint32_t g_bad_stream_at = ~0u, g_bad_model_at = ~0u;  // the call whose decode / rANS launch raises its status bit
+static uint32_t coded_size(uint32_t s, uint32_t call) { return 4u * (1u + (s + call) % 5u); }
+static uint8_t coded_byte(uint32_t call) { return (uint8_t)(0x41u + call % 23u); }
+static uint8_t decoded_byte(uint32_t s, uint32_t call) { return (uint8_t)((0x61u + call % 19u) ^ (s << 5)); }
+static uint32_t consumed_words(uint32_t call) { return 1u + call % 7u; }
+static void rans_effect(const fakehip::Launch& l) {
+    const divans_hip::RansBatch& r = *(const divans_hip::RansBatch*)l.args.data();
+    for (uint32_t s = 0; s < r.n_streams; ++s) {
+        const uint32_t size = (uint32_t)std::min<uint64_t>(coded_size(s, g_call), r.out_slot);
+        r.out_sizes[s] = size; r.out_offsets[s] = (uint64_t)s * r.out_slot + r.out_slot - size;
+        std::memset(r.out + r.out_offsets[s], coded_byte(g_call), size);
+        if (r.chunk_bytes) r.chunk_bytes[(size_t)s * r.max_chunks] = size;
+    }
+    if (g_bad_model_at == g_call) *r.status |= DIVANS_GPU_STATUS_BAD_MODEL;      // where the real pass meets an invalid (start, freq)
+}
+static void decode_effect(const fakehip::Launch& l) {
+    const divans_hip::LitBatch& b = *(const divans_hip::LitBatch*)l.args.data();
+    for (uint32_t s = 0; s < b.n_streams; ++s) {
+        const uint64_t off = b.out_offsets ? b.out_offsets[s] : (uint64_t)s * b.stream_len;
+        std::memset(b.out + off, decoded_byte(s, g_call), b.out_sizes ? b.out_sizes[s] : b.stream_len);
+        if (b.consumed) b.consumed[s] = consumed_words(g_call);
+    }
+    if (g_bad_stream_at == g_call) { *b.status |= DIVANS_GPU_STATUS_BAD_STREAM; if (b.stream_bad && b.n_streams > 3) b.stream_bad[3] = 1; }
+}
+// the pack pass as the kernels do it (lit_kernels.hip, scan_sizes_kernel / pack_copy_kernel): what encode_packed, the host wrappers
+// and the caller read back is then the sum and the bytes of THIS call's sizes
+static void scan_effect(const fakehip::Launch& l) {
+    const fakehip::ScanArgs& a = *(const fakehip::ScanArgs*)l.args.data();
+    uint64_t run = a.accumulate ? *a.total : 0;
+    for (uint32_t i = 0; i < a.n; ++i) { a.offsets[i] = run; run += (a.sizes[i] + 3u) & ~3u; }
+    *a.total = run;
+}
+static void pack_effect(const fakehip::Launch& l) {
+    const fakehip::PackArgs& a = *(const fakehip::PackArgs*)l.args.data();
+    for (uint32_t s = 0; s < a.n; ++s) {
+        const uint64_t bytes = ((uint64_t)a.sizes[s] + 3u) & ~3ull;
+        if (a.dst_off[s] + bytes > a.cap) { if (a.status) *a.status |= DIVANS_GPU_STATUS_OUTPUT_FULL; continue; }
+        std::memcpy(a.packed + a.dst_off[s], a.slots + a.src_off[s], a.sizes[s]);
+    }
+}
+static void stream_effects() {
+    fakehip::set_effect("lit_commands_prepare", prepare_effect);
+    fakehip::set_effect("rans_", rans_effect);
+    fakehip::set_effect("lit_decode", decode_effect);
+    fakehip::set_effect("scan_sizes_kernel", scan_effect);
+    fakehip::set_effect("pack_copy_kernel", pack_effect);
+}
+
+static void non_blocking_stream() {
+    if (hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking) != hipSuccess) { fprintf(stderr, "driver: hipStreamCreateWithFlags failed\n"); exit(2); }
+    EXPECT(fakehip::stream_kind(g_stream) == fakehip::STREAM_NON_BLOCKING, "the driver's stream is not a non-blocking one");
+}
+static void drop_stream() {
+    EXPECT(fakehip::pending_entries(g_stream) == 0, "%zu entries of the caller's stream are still in flight at the end", fakehip::pending_entries(g_stream));
+    (void)hipStreamDestroy(g_stream); g_stream = nullptr;
+}
+
+// every value a call under test reads back is this call's, not the previous call's and not the buffer's first contents
+struct HostOut {
+    std::vector<uint8_t> packed; std::vector<uint64_t> off; std::vector<uint32_t> sz, chunks; size_t total = 0x5a5a5a5a;
+    explicit HostOut(uint32_t n, size_t cap) : packed(cap, 0xEE), off(n, 0xEEEEEEEEEEEEEEEEull), sz(n, 0xEEEEEEEEu), chunks((size_t)n * 2u, 0xEEEEEEEEu) {}
+};
+// what an encode wrapper returns for `n` streams coded in slices of `S` (the effects number a slice's streams from 0)
+static void expect_encoded(const char* what, uint32_t call, uint32_t n, uint32_t S, const uint8_t* packed, const uint64_t* off, const uint32_t* sz, size_t total, const uint32_t* chunks) {
+    uint64_t run = 0;
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t want = coded_size(s % S, call);
+        EXPECT(sz[s] == want, "%s, call %u: size of stream %u is %u, this call's launch wrote %u (the previous call's: %u)", what, call, s, sz[s], want, coded_size(s % S, call - 1));
+        EXPECT(off[s] == run, "%s, call %u: offset of stream %u is %llu, not %llu", what, call, s, (unsigned long long)off[s], (unsigned long long)run);
+        for (uint32_t k = 0; k < want; ++k) EXPECT(packed[run + k] == coded_byte(call), "%s, call %u: byte %u of stream %u is 0x%02x, this call's launch wrote 0x%02x", what, call, k, s, packed[run + k], coded_byte(call));
+        if (chunks) EXPECT(chunks[2u * s] == want && chunks[2u * s + 1u] == 0u, "%s, call %u: chunk sizes of stream %u are %u, %u", what, call, s, chunks[2u * s], chunks[2u * s + 1u]);
+        run += want;      // sizes are multiples of 4
+    }
+    EXPECT(total == run, "%s, call %u: total %zu, this call's launches come to %llu", what, call, total, (unsigned long long)run);
+}
+static void expect_decoded(const char* what, uint32_t call, uint32_t n, uint32_t S, uint32_t len, const uint8_t* out) {
+    for (uint32_t s = 0; s < n; ++s) for (uint32_t k = 0; k < len; k += len - 1u)
+        EXPECT(out[(size_t)s * len + k] == decoded_byte(s % S, call), "%s, call %u: byte %u of stream %u is 0x%02x, this call's launch wrote 0x%02x", what, call, k, s, out[(size_t)s * len + k], decoded_byte(s % S, call));
+}
+static void host_entry_points(const Config& cf) {
+    const uint32_t n = 37, len = 300;
+    const std::string base = cf.name + "/host";
+    divans_gpu_codec* c = make_codec(cf, 40000);
+    std::vector<uint8_t> in((size_t)n * len, 0x20);
+    const size_t cap = (size_t)n * divans_gpu_lit_encode_bound(len);
+    std::vector<uint64_t> last_off; std::vector<uint32_t> last_sz; std::vector<uint8_t> last_packed;
+    for (int round = 0; round < 2; ++round) {      // every buffer and the codec are used twice: a stale read returns the other round's well-formed values
+        label(base + "/encode_host");
+        { HostOut o(n, cap); ++g_call;
+          OK(divans_gpu_lit_encode_host(c, in.data(), len, n, o.packed.data(), cap, o.off.data(), o.sz.data(), &o.total));
+          expect_encoded("encode_host", g_call, n, n, o.packed.data(), o.off.data(), o.sz.data(), o.total, nullptr); }
+        label(base + "/encode_host_chunks");
+        { HostOut o(n, cap); ++g_call;
+          OK(divans_gpu_lit_encode_host_chunks(c, in.data(), len, n, o.packed.data(), cap, o.off.data(), o.sz.data(), &o.total, o.chunks.data(), 2));
+          expect_encoded("encode_host_chunks", g_call, n, n, o.packed.data(), o.off.data(), o.sz.data(), o.total, o.chunks.data());
+          last_off = o.off; last_sz = o.sz; last_packed = o.packed; }
+        label(base + "/encode_host/bad_model");
+        { HostOut o(n, cap); ++g_call; g_bad_model_at = g_call;
+          const int rc = divans_gpu_lit_encode_host(c, in.data(), len, n, o.packed.data(), cap, o.off.data(), o.sz.data(), &o.total);
+          EXPECT(rc == DIVANS_GPU_EINVAL, "the call whose model launch raised BAD_MODEL returns %d", rc);
+          ++g_call;
+          OK(divans_gpu_lit_encode_host(c, in.data(), len, n, o.packed.data(), cap, o.off.data(), o.sz.data(), &o.total));      // the word was this call's own again
+          expect_encoded("encode_host after a refused call", g_call, n, n, o.packed.data(), o.off.data(), o.sz.data(), o.total, nullptr); }
+        label(base + "/decode_host");
+        { std::vector<uint8_t> out((size_t)n * len, 0xEE); ++g_call;
+          OK(divans_gpu_lit_decode_host(c, last_packed.data(), last_off.data(), last_sz.data(), n, out.data(), len));
+          expect_decoded("decode_host", g_call, n, n, len, out.data());
+          ++g_call; g_bad_stream_at = g_call;
+          const int rc = divans_gpu_lit_decode_host(c, last_packed.data(), last_off.data(), last_sz.data(), n, out.data(), len);
+          EXPECT(rc == DIVANS_GPU_ECORRUPT, "the call whose decode launch raised BAD_STREAM returns %d", rc);
+          ++g_call;
+          OK(divans_gpu_lit_decode_host(c, last_packed.data(), last_off.data(), last_sz.data(), n, out.data(), len));
+          expect_decoded("decode_host after a refused call", g_call, n, n, len, out.data()); }
+        for (uint32_t S : {37u, 13u, 6u}) for (int pinned = 0; pinned < 2; ++pinned) {      // 1, 3 and 7 slices, into page-locked and into pageable memory
+            label(base + "/pipelined/" + std::to_string((n + S - 1u) / S) + (pinned ? "_slices_pinned" : "_slices_pageable"));
+            HostOut o(n, cap);
+            uint8_t* h_in = pinned ? (uint8_t*)divans_gpu_host_alloc(in.size()) : in.data();
+            uint8_t* h_packed = pinned ? (uint8_t*)divans_gpu_host_alloc(cap) : o.packed.data();
+            uint8_t* h_out = pinned ? (uint8_t*)divans_gpu_host_alloc(in.size()) : nullptr;
+            std::vector<uint8_t> out_pageable(in.size(), 0xEE);
+            if (!h_out) h_out = out_pageable.data();
+            EXPECT(h_in && h_packed && h_out, "divans_gpu_host_alloc");
+            if (pinned) { std::memcpy(h_in, in.data(), in.size()); std::memset(h_packed, 0xEE, cap); std::memset(h_out, 0xEE, in.size()); }
+            ++g_call;
+            OK(divans_gpu_lit_encode_host_pipelined(c, h_in, len, n, h_packed, cap, o.off.data(), o.sz.data(), &o.total, S));
+            expect_encoded("encode_host_pipelined", g_call, n, S, h_packed, o.off.data(), o.sz.data(), o.total, nullptr);
+            ++g_call;
+            OK(divans_gpu_lit_decode_host_pipelined(c, h_packed, o.off.data(), o.sz.data(), n, h_out, len, S));
+            expect_decoded("decode_host_pipelined", g_call, n, S, len, h_out);
+            ++g_call; g_bad_stream_at = g_call;
+            const int rc = divans_gpu_lit_decode_host_pipelined(c, h_packed, o.off.data(), o.sz.data(), n, h_out, len, S);
+            EXPECT(rc == DIVANS_GPU_ECORRUPT, "the pipelined call whose decode launch raised BAD_STREAM returns %d", rc);
+            if (pinned) { divans_gpu_host_free(h_in); divans_gpu_host_free(h_packed); divans_gpu_host_free(h_out); }
+        }
+    }
+    // one stream piece by piece: 20 000 + 20 000 bytes complete one 65 536-symbol chunk, _finish codes the open one
+    for (int round = 0; round < 2; ++round) {
+        label(base + "/stream_encode");
+        std::vector<uint8_t> piece(20000, 0x33), out(divans_gpu_lit_encode_bound(65536), 0xEE);
+        uint32_t sizes[4] = {0xEEEEEEEEu, 0xEEEEEEEEu, 0, 0}, chunks = 99; size_t out_len = 0x5a5a;
+        OK(divans_gpu_lit_stream_begin(c));
+        ++g_call;
+        OK(divans_gpu_lit_stream_encode(c, piece.data(), 20000, 0, out.data(), out.size(), sizes, 4, &chunks, &out_len));
+        EXPECT(chunks == 0 && out_len == 0, "the first piece completes no chunk (%u, %zu)", chunks, out_len);
+        ++g_call;
+        OK(divans_gpu_lit_stream_encode(c, piece.data(), 20000, 0x0807060504030201ull, out.data(), out.size(), sizes, 4, &chunks, &out_len));
+        EXPECT(chunks == 1 && sizes[0] == coded_size(0, g_call) && out_len == sizes[0] && out[0] == coded_byte(g_call) && out[out_len - 1] == coded_byte(g_call),
+               "stream_encode, call %u: %u chunks, size %u (this call's launch wrote %u), %zu bytes, first 0x%02x", g_call, chunks, sizes[0], coded_size(0, g_call), out_len, out[0]);
+        ++g_call; out_len = 0x5a5a;
+        OK(divans_gpu_lit_stream_finish(c, out.data(), out.size(), &out_len));
+        EXPECT(out_len == coded_size(0, g_call) && out[0] == coded_byte(g_call), "stream_finish, call %u: %zu bytes, first 0x%02x", g_call, out_len, out[0]);
+        label(base + "/stream_decode");
+        std::vector<uint8_t> coded(4096, 0x11), back(32768, 0xEE);
+        OK(divans_gpu_lit_stream_decode_begin(c));
+        for (int k = 0; k < 2; ++k) {
+            size_t consumed = 0x5a5a; ++g_call;
+            OK(divans_gpu_lit_stream_decode(c, coded.data(), coded.size(), k ? 1000u : 32768u, 0, back.data(), &consumed));
+            EXPECT(consumed == 4u * consumed_words(g_call) && back[0] == decoded_byte(0, g_call) && back[k ? 999 : 32767] == decoded_byte(0, g_call),
+                   "stream_decode, call %u: consumed %zu (this call's launch wrote %u words), first byte 0x%02x", g_call, consumed, consumed_words(g_call), back[0]);
+        }
+        ++g_call; g_bad_stream_at = g_call;
+        size_t consumed = 0;
+        const int rc = divans_gpu_lit_stream_decode(c, coded.data(), coded.size(), 1000u, 0, back.data(), &consumed);
+        EXPECT(rc == DIVANS_GPU_ECORRUPT, "the stream_decode call whose launch raised BAD_STREAM returns %d", rc);
+        // the device-pointer calls are open again once no stream is: begin + finish with nothing pending
+        OK(divans_gpu_lit_stream_begin(c)); out_len = 1; OK(divans_gpu_lit_stream_finish(c, out.data(), out.size(), &out_len)); EXPECT(out_len == 0, "an empty stream finishes with %zu bytes", out_len);
+    }
+    {   // the primitives' test entry points copy in, launch, copy out and wait on the codec's stream as well
+        label(base + "/selftests");
+        uint64_t mismatches = 1; OK(divans_gpu_selftest_division(c, &mismatches));
+        const uint32_t ops[8] = {6, 0, 0, 0, 6, 0, 0, 0}; int32_t rec[32];
+        OK(divans_gpu_selftest_cdf_ops(c, ops, 2, rec)); OK(divans_gpu_selftest_cdf_ops_on(c, 1, ops, 2, rec));
+        const uint32_t pairs[4] = {1u << 16, 1u << 16, 1u << 16, 1u << 16}; uint8_t coded[256]; size_t coded_len = 0x5a5a;
+        ++g_call;
+        OK(divans_gpu_selftest_rans_pairs(c, pairs, 4, coded, sizeof(coded), &coded_len));
+        EXPECT(coded_len == coded_size(0, g_call) && coded[0] == coded_byte(g_call), "selftest_rans_pairs, call %u: %zu bytes, first 0x%02x", g_call, coded_len, coded[0]);
+    }
+    divans_gpu_codec_destroy(c);
+}
+
+// the status calls and pack_streams on the caller's stream: each reports its own launch
+static void status_calls(const Config& cf) {
+    label(cf.name + "/status");
+    divans_gpu_codec* c = make_codec(cf, 300);
+    Batch b = make_batch(ragged(37, 300), 300, cf.btype);
+    uint8_t* d_flags = dev_bytes(64);
+    uint32_t* h_word = (uint32_t*)divans_gpu_host_alloc(sizeof(uint32_t));
+    EXPECT(h_word != nullptr, "divans_gpu_host_alloc");
+    OK(divans_gpu_codec_set_stream_flags(c, d_flags));
+    for (int round = 0; round < 2; ++round) {
+        uint32_t status = 0xEEEEEEEEu;
+        ++g_call; OK(decode_batch(c, b));
+        OK(divans_gpu_codec_status(c, &status)); EXPECT(status == 0, "status after a clean decode is %u", status);
+        ++g_call; g_bad_stream_at = g_call; OK(decode_batch(c, b));
+        *h_word = 0xEEEEEEEEu;
+        OK(divans_gpu_codec_status_async(c, h_word));
+        EXPECT(*h_word == 0xEEEEEEEEu, "status_async wrote the word (%u) before anything waited: the copy is not stream-ordered", *h_word);
+        EXPECT(hipStreamSynchronize(g_stream) == hipSuccess, "sync");
+        EXPECT(*h_word == DIVANS_GPU_STATUS_BAD_STREAM, "status_async behind a failing decode reports %u", *h_word);
+        uint8_t flags[37];
+        (void)hipMemcpy(flags, d_flags, 37, hipMemcpyDeviceToHost);
+        for (uint32_t s = 0; s < 37; ++s) EXPECT(flags[s] == (s == 3 ? 1 : 0), "flag of stream %u is %u", s, flags[s]);
+        (void)hipMemset(d_flags, 0, 64);
+        // clear_status queued behind the failing call clears its bit; a later call's bit is kept
+        OK(divans_gpu_codec_clear_status(c));
+        *h_word = 0xEEEEEEEEu; OK(divans_gpu_codec_status_async(c, h_word));
+        ++g_call; g_bad_model_at = g_call; OK(encode_batch(c, b));
+        OK(divans_gpu_codec_status(c, &status));
+        EXPECT(*h_word == 0, "status_async behind clear_status reports %u", *h_word);
+        EXPECT(status == DIVANS_GPU_STATUS_BAD_MODEL, "status reports %u: the bit of the call behind clear_status alone is %u", status, DIVANS_GPU_STATUS_BAD_MODEL);
+        OK(divans_gpu_codec_status(c, &status)); EXPECT(status == 0, "status read twice reports %u the second time", status);
+        // pack_streams on this call's sizes: total and offsets are the prefix sums of what the launch in front wrote
+        ++g_call; OK(encode_batch(c, b));
+        OK(divans_gpu_pack_streams(c, b.d_slots, b.d_out_off, b.d_out_sz, b.n, b.d_packed, b.d_packed_off, b.d_total));
+        EXPECT(hipStreamSynchronize(g_stream) == hipSuccess, "sync");
+        uint64_t total = 0, want = 0; std::vector<uint64_t> poff(b.n);
+        (void)hipMemcpy(&total, b.d_total, 8, hipMemcpyDeviceToHost); (void)hipMemcpy(poff.data(), b.d_packed_off, 8u * b.n, hipMemcpyDeviceToHost);
+        for (uint32_t s = 0; s < b.n; ++s) { EXPECT(poff[s] == want, "pack_streams: offset %u", s); want += coded_size(s, g_call); }
+        EXPECT(total == want, "pack_streams: total %llu, this call's sizes come to %llu", (unsigned long long)total, (unsigned long long)want);
+    }
+    divans_gpu_codec_destroy(c);
+    divans_gpu_host_free(h_word);
+    free_mine();
+}
+
+// the setters with work in flight: each is called behind a launch nothing has waited for, and the same call is made again
+static void setters_in_flight(const Config& cf, uint32_t types_a, uint32_t types_b) {
+    label(cf.name + "/setters_in_flight");
+    divans_gpu_codec* c = make_codec(cf, 300);
+    OK(divans_gpu_codec_set_block_types(c, types_a));
+    Batch b = make_batch(ragged(37, 300), 300, cf.btype);
+    auto work = [&]() { ++g_call; OK(encode_segments(c, b)); ++g_call; OK(decode_segments(c, b)); ++g_call; OK(encode_batch(c, b)); ++g_call; OK(decode_batch(c, b)); };
+    auto tried = [&](int rc, const char* what) { EXPECT(rc == 0 || rc == DIVANS_GPU_EINVAL, "%s: %d %s", what, rc, divans_gpu_last_error()); };
+    const uint32_t rows[4] = {32, 0, 0, 0}, shifts[4] = {5, 5, 0, 0};
+    work(); OK(divans_gpu_codec_set_block_types(c, types_b));
+    work(); OK(divans_gpu_codec_set_block_types(c, types_a));
+    work(); tried(divans_gpu_codec_set_geometry(c, 64, 0xffffffffu), "set_geometry");
+    work(); tried(divans_gpu_codec_set_decoder(c, 3, rows, shifts, 0), "set_decoder");
+    work(); tried(divans_gpu_codec_set_split_cache(c, 32, 0), "set_split_cache");
+    for (uint32_t order : {2u, 1u, 0u}) { work(); OK(divans_gpu_codec_set_byte_order(c, order)); }
+    work(); tried(divans_gpu_codec_set_high_row_pinning(c, 2), "set_high_row_pinning");
+    work(); tried(divans_gpu_codec_set_encode_path(c, 2), "set_encode_path");
+    work(); tried(divans_gpu_codec_set_bucket_batch(c, 16), "set_bucket_batch");
+    work(); tried(divans_gpu_codec_set_rans_split(c, 1), "set_rans_split");
+    work(); tried(divans_gpu_codec_tune_tables(c, 1), "tune_tables");
+    work();
+    uint32_t mode = 0, ready = 0, slots = 0, distance = 0; uint8_t rank[256]; float ms = 0.f;
+    OK(divans_gpu_codec_byte_order(c, &mode, &ready, rank));
+    OK(divans_gpu_codec_high_row_slots(c, &slots)); OK(divans_gpu_codec_bucket_stride(c, &distance));
+    ++g_call; OK(encode_commands(c, b, false)); OK(divans_gpu_codec_last_prepare_ms(c, &ms));
+    uint32_t* d_chunks = (uint32_t*)dev_bytes((size_t)b.n * 8u);
+    ++g_call; OK(divans_gpu_lit_encode_batch_chunks(c, b.d_in, b.d_off, b.d_sz, b.longest, b.n, b.d_slots, b.slot, b.d_out_off, b.d_out_sz, d_chunks, 2));
+    uint32_t status = 0; OK(divans_gpu_codec_status(c, &status));
+    divans_gpu_codec_destroy(c);
+    free_mine();
+}
+
+static void scenario_streams_small() {
+    non_blocking_stream();
+    stream_effects();
+    scenario_small();      // scenario 1's call table, every codec on the caller's stream
+    for (const char* name : {"simple", "mixing"}) { status_calls(config(name)); setters_in_flight(config(name), 8, 2); }
+    setters_in_flight(config("context_keyed"), 8, 2);
+    clean_end();
+    drop_stream();
+}
+static void scenario_streams_placement() {
+    non_blocking_stream();
+    scenario_placement();
+    drop_stream();
+}
+static void scenario_streams_host() {
+    non_blocking_stream();
+    stream_effects();
+    host_entry_points(config("simple"));
+    host_entry_points(config("mixing"));
+    clean_end();
+    drop_stream();
+}
+
 int main(int argc, char** argv) {
-    if (argc < 4) { fprintf(stderr, "usage: capi_contract <small|m6|placement|pool|failures> <configs> <trace> [<sizes>]\n"); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: capi_contract <small|m6|placement|pool|failures|streams_small|streams_placement|streams_host> <configs> <trace> [<sizes>]\n"); return 2; }
     load_configs(argv[2]);
     fakehip::open_trace(argv[3]);
     const std::string s = argv[1];
@@ -652,6 +941,9 @@ int main(int argc, char** argv) {
     else if (s == "placement") scenario_placement();
     else if (s == "pool") scenario_pool();
     else if (s == "failures") scenario_failures();
+    else if (s == "streams_small") scenario_streams_small();
+    else if (s == "streams_placement") scenario_streams_placement();
+    else if (s == "streams_host") scenario_streams_host();
     else return 2;
     printf("%s: %zu launches, contract held\n", s.c_str(), fakehip::launches().size());
     return 0;

@@ -2,7 +2,8 @@
 // Defines every runtime symbol the host-only objects of divans_amd/csrc/*.hip and capi.cpp reference.  Compiled against the real HIP
 // headers for their types only and never linked with libamdhip64: no kernel code runs and no GPU is touched.  Memory is address
 // ranges of lazily committed anonymous mappings, so a codec with gigabytes of tables and tens of gigabytes of work arrays can be
-// "allocated"; streams and events are queues; every launch is recorded with its argument structs and checked against the layouts
+// "allocated"; streams have a kind (null, blocking, non-blocking) and a queue whose entries carry the bytes they read and write, and two
+// unordered entries of different streams on the same bytes are an `order` violation (README, "The stream model"); every launch is recorded with its argument structs and checked against the layouts
 // documented in divans_amd/csrc/lit_kernels.h at once.  A violation ends the program with a message naming the kernel and the field.
 #include "fakehip_rt.h"
 
@@ -37,10 +38,28 @@ struct Range {
     bool sealed = false;            // hipMemSetAccess has completed a mapping: nothing more may be mapped until all of it is gone
 };
 struct Phys { size_t bytes; int device; bool released; int mapped; };
-struct Event { void* stream = nullptr; uint64_t seq = 0; bool recorded = false; };
+typedef std::map<void*, uint64_t> Clock;        // stream -> the last entry of it that is ordered before (an edge of hipStreamWaitEvent or of the legacy null stream)
+struct Event { void* stream = nullptr; uint64_t seq = 0; bool recorded = false; uint64_t id = 0; Clock clock; };
 struct Failure { std::string fn; uint64_t at; hipError_t e; bool global; };
+// One entry of a stream's queue (README "The stream model").  What an entry does to DEVICE memory is carried out when it is enqueued
+// -- program order is one valid order of the device's work as long as the `order` rule holds, and the launch contract reads offset
+// and size arrays the copies in front of a launch brought --; what the HOST can see of an entry of a non-blocking stream (the
+// destination of a device-to-host copy, the end of a launch) arrives when the entry completes.
+enum OpType { OP_LAUNCH, OP_COPY, OP_FILL, OP_RECORD, OP_WAIT };
+struct Op {
+    uint64_t id = 0; void* stream = nullptr; int type = OP_COPY; std::string what;
+    uint64_t launch_seq = 0;
+    std::vector<fakehip::Span> spans;
+    Clock clock;
+    // a device-to-host copy of a non-blocking stream: the source as it was at this place of the queue, delivered at completion
+    void* dst = nullptr; size_t dpitch = 0, width = 0, height = 0; std::vector<uint8_t> staged; bool deferred = false;
+    // a copy from page-locked memory reads its source when it runs: the bytes must still be those it was enqueued with
+    const void* pinned_src = nullptr; std::vector<uint8_t> pinned_copy;
+};
+struct StreamState { int kind = fakehip::STREAM_NULL; uint64_t last = 0; Clock clock; bool alive = true; };
 
 std::recursive_mutex g_mu;
+#define LOCK std::lock_guard<std::recursive_mutex> lock_(g_mu)
 std::map<uintptr_t, Range> g_ranges;           // by base; dead blocks leave (their addresses are unmapped), reserved ranges stay
 std::vector<Range> g_dead;                     // freed blocks, for the ledger and for messages
 std::map<uint64_t, Phys> g_phys;
@@ -117,11 +136,103 @@ size_t extent_at(uintptr_t p, Range** out = nullptr) {
     return end - at;
 }
 
-bool any_in_flight_on(uint64_t born, std::string* who) {
-    for (const fakehip::Launch& l : g_launches)
-        if (l.in_flight && std::find(l.refs.begin(), l.refs.end(), born) != l.refs.end()) { *who = l.kernel + " (launch " + std::to_string(l.seq) + ")"; return true; }
+// ---- the stream model ---------------------------------------------------------------------------------------------------------------
+std::map<void*, StreamState> g_streams;        // the null stream is g_streams[nullptr]
+std::deque<Op> g_pending;                      // entries nothing has completed yet, by id
+uint64_t g_op = 0;
+std::vector<std::pair<uint64_t, std::string>> g_unordered_ok;      // allow_unordered: `born` of the range, why
+
+StreamState& stream_state(void* s) {
+    auto it = g_streams.find(s);
+    if (it == g_streams.end()) {
+        if (s != nullptr) fakehip::violation("(runtime)", "stream", "a call names a stream that was never created (or is destroyed)");
+        it = g_streams.emplace(s, StreamState()).first;
+    }
+    return it->second;
+}
+void merge(Clock& into, const Clock& from) { for (const auto& kv : from) { uint64_t& v = into[kv.first]; v = std::max(v, kv.second); } }
+void merge(Clock& into, void* s, uint64_t id) { if (id) { uint64_t& v = into[s]; v = std::max(v, id); } }
+bool allowed_unordered(uint64_t born) {
+    for (const auto& a : g_unordered_ok) if (a.first == born) return true;
     return false;
 }
+std::string op_name(const Op& p) { return p.what + " (entry " + std::to_string(p.id) + " of stream " + (p.stream ? "0x" + std::to_string((uintptr_t)p.stream % 100000) : std::string("null")) + ")"; }
+
+// a lifetime question: does an entry still in flight reference the range?  On the null stream and on blocking streams only launches
+// count, as before there were queues (a copy there is carried out at once); on a non-blocking stream every entry does
+bool any_in_flight_on(uint64_t born, std::string* who) {
+    for (const Op& p : g_pending) {
+        if (p.type != OP_LAUNCH && stream_state(p.stream).kind != fakehip::STREAM_NON_BLOCKING) continue;
+        for (const fakehip::Span& s : p.spans) if (s.born == born) { *who = p.type == OP_LAUNCH ? p.what + " (launch " + std::to_string(p.launch_seq) + ")" : op_name(p); return true; }
+    }
+    return false;
+}
+
+// the `order` rule: `spans` of a new entry of `stream` (or of the host: a synchronous copy, a map; host = true) against every entry
+// in flight on another stream that no edge puts in front of it
+void check_order(const std::string& what, void* stream, bool host, const Clock& clock, const std::vector<fakehip::Span>& spans) {
+    if (spans.empty()) return;
+    for (const Op& p : g_pending) {
+        if (p.spans.empty()) continue;
+        if (host) { if (stream_state(p.stream).kind != fakehip::STREAM_NON_BLOCKING) continue; }      // a synchronous call waits for the null stream and the blocking ones itself
+        else {
+            if (p.stream == stream) continue;
+            auto it = clock.find(p.stream);
+            if (it != clock.end() && it->second >= p.id) continue;
+        }
+        for (const fakehip::Span& a : p.spans) for (const fakehip::Span& b : spans) {
+            if (a.born != b.born || !(a.write || b.write) || a.lo >= b.hi || b.lo >= a.hi) continue;
+            if (allowed_unordered(a.born)) continue;
+            fakehip::violation(what, "order", std::string(b.write ? "writes" : "reads") + " " + std::to_string(std::min(a.hi, b.hi) - std::max(a.lo, b.lo)) + " bytes of allocation " + std::to_string(a.born) +
+                               " that " + op_name(p) + " " + (a.write ? "writes" : "reads") + ", still in flight, and no event, wait or synchronisation orders the two");
+        }
+    }
+}
+
+// the legacy null stream waits for every blocking stream and every blocking stream for it
+void legacy_edges(void* s, StreamState& st) {
+    if (st.kind == fakehip::STREAM_NULL) { for (auto& kv : g_streams) if (kv.second.kind == fakehip::STREAM_BLOCKING) { merge(st.clock, kv.first, kv.second.last); merge(st.clock, kv.second.clock); } }
+    else if (st.kind == fakehip::STREAM_BLOCKING) { StreamState& n = stream_state(nullptr); merge(st.clock, nullptr, n.last); merge(st.clock, n.clock); }
+    (void)s;
+}
+Op& enqueue(Op op) {
+    StreamState& st = stream_state(op.stream);
+    legacy_edges(op.stream, st);
+    check_order(op.what, op.stream, false, st.clock, op.spans);
+    op.id = ++g_op; op.clock = st.clock; st.last = op.id;
+    g_pending.push_back(std::move(op));
+    return g_pending.back();
+}
+void finish(Op& p) {
+    if (p.deferred) for (size_t i = 0; i < p.height; ++i) std::memcpy((uint8_t*)p.dst + i * p.dpitch, p.staged.data() + i * p.width, p.width);
+    if (p.pinned_src && std::memcmp(p.pinned_src, p.pinned_copy.data(), p.pinned_copy.size()) != 0)
+        fakehip::violation(p.what, "order", "the page-locked source of " + op_name(p) + " was changed by the host while the copy was in flight");
+    if (p.type == OP_LAUNCH) g_launches[p.launch_seq - 1].in_flight = false;
+}
+// completes the entries `pick` names and whatever they wait for, oldest first
+template <class Pick> void complete_where(Pick pick) {
+    std::vector<char> take(g_pending.size(), 0);
+    bool any = false;
+    for (size_t i = 0; i < g_pending.size(); ++i) if (pick(g_pending[i])) { take[i] = 1; any = true; }
+    if (!any) return;
+    for (bool moved = true; moved;) {
+        moved = false;
+        Clock need;
+        for (size_t i = 0; i < g_pending.size(); ++i) if (take[i]) { merge(need, g_pending[i].clock); merge(need, g_pending[i].stream, g_pending[i].id); }
+        for (size_t i = 0; i < g_pending.size(); ++i) {
+            if (take[i]) continue;
+            auto it = need.find(g_pending[i].stream);
+            if (it != need.end() && g_pending[i].id <= it->second) { take[i] = 1; moved = true; }
+        }
+    }
+    std::deque<Op> rest;
+    for (size_t i = 0; i < g_pending.size(); ++i) { if (take[i]) finish(g_pending[i]); else rest.push_back(std::move(g_pending[i])); }
+    g_pending.swap(rest);
+}
+void complete_stream(void* s, uint64_t upto) { complete_where([&](const Op& p) { return p.stream == s && p.id <= upto; }); }
+// a synchronous hipMemcpy / hipMemset / hipFree: the null stream and every blocking stream, not a non-blocking one
+void complete_legacy() { complete_where([&](const Op& p) { return stream_state(p.stream).kind != fakehip::STREAM_NON_BLOCKING; }); }
+void span_of(std::vector<fakehip::Span>& out, const void* p, size_t bytes, bool write);
 
 void* map_pages(size_t bytes, int prot) {
     bytes = (bytes + kPage - 1) / kPage * kPage;
@@ -159,18 +270,13 @@ hipError_t free_block(void* p, const char* fn, int kind) {
     return hipSuccess;
 }
 
-void complete(void* stream, uint64_t upto, bool every_stream) {
-    for (fakehip::Launch& l : g_launches)
-        if (l.in_flight && (every_stream || l.stream == stream) && l.seq <= upto) l.in_flight = false;
-}
-
 // ---- the launch contract -----------------------------------------------------------------------------------------------------
 struct Checker {
     fakehip::Launch& l;
     explicit Checker(fakehip::Launch& launch) : l(launch) {}
     [[noreturn]] void bad(const std::string& field, const std::string& what) const { fakehip::violation(l.kernel, field, what); }
     // `bytes` from p lie in one live extent (a null pointer is the caller's business: `optional`)
-    void need(const char* field, const void* p, uint64_t bytes, bool optional = false) {
+    void need(const char* field, const void* p, uint64_t bytes, bool optional = false, bool write = true) {
         if (!p) { if (optional) return; bad(field, "null"); }
         Range* r = nullptr;
         const size_t have = extent_at((uintptr_t)p, &r);
@@ -180,26 +286,31 @@ struct Checker {
         if (bytes > have) bad(field, "needs " + std::to_string(bytes) + " bytes, the live extent from there holds " + std::to_string(have));
         r->last_launch = l.seq;
         if (std::find(l.refs.begin(), l.refs.end(), r->born) == l.refs.end()) l.refs.push_back(r->born);
+        l.spans.push_back({r->born, (uintptr_t)p, (uintptr_t)p + std::max<uint64_t>(bytes, 1), write});
     }
+    void ro(const char* field, const void* p, uint64_t bytes, bool optional = false) { need(field, p, bytes, optional, false); }      // the struct declares the pointer const
     // per-stream ranges base + off[s] .. + size[s] (or the uniform layout s * stream_len); the arrays themselves are checked first
-    void ranges(const char* field, const uint8_t* base, const uint64_t* off, const uint32_t* sizes, uint32_t n, uint64_t uniform, bool optional = false) {
+    void ranges(const char* field, const uint8_t* base, const uint64_t* off, const uint32_t* sizes, uint32_t n, uint64_t uniform, bool optional = false, bool write = false) {
         if (!base) { if (optional) return; bad(field, "null"); }
         const std::string f = field;
-        if (off) { need((f + "_offsets").c_str(), off, (uint64_t)n * 8u); need((f + "_sizes").c_str(), sizes, (uint64_t)n * 4u); }
+        if (off) { ro((f + "_offsets").c_str(), off, (uint64_t)n * 8u); ro((f + "_sizes").c_str(), sizes, (uint64_t)n * 4u); }
         Range* r = nullptr;
         const size_t have = extent_at((uintptr_t)base, &r);
         if (!r || !r->alive || have == 0) { need(field, base, 1); return; }
-        need(field, base, 1);
+        need(field, base, 1, false, write);
+        uint64_t lo = ~0ull, hi = 0;
         for (uint32_t s = 0; s < n; ++s) {
             const uint64_t a = off ? off[s] : (uint64_t)s * uniform, b = off ? sizes[s] : uniform;
             if (a + b > have || a + b < a) bad(f + "_offsets[" + std::to_string(s) + "] + " + f + "_sizes", "the stream's range ends at " + std::to_string(a + b) + ", the live extent holds " + std::to_string(have));
+            if (b) { lo = std::min(lo, a); hi = std::max(hi, a + b); }
         }
+        if (hi > lo) l.spans.push_back({r->born, (uintptr_t)base + lo, (uintptr_t)base + hi, write});      // what the streams of this launch cover, not the whole block
     }
     void seg_list(const uint32_t* seg_begin, const void* segs, uint32_t n, const char* begin_name, const char* list_name, size_t record) {
         if (!seg_begin && !segs) return;
-        need(begin_name, seg_begin, ((uint64_t)n + 1u) * 4u);
+        ro(begin_name, seg_begin, ((uint64_t)n + 1u) * 4u);
         const uint64_t last = seg_begin[n];
-        if (last) need(list_name, segs, last * record); else need(list_name, segs, 1);
+        if (last) ro(list_name, segs, last * record); else ro(list_name, segs, 1);
     }
     void lds_rules(const void* fn, bool persistent) {
         auto it = g_max_dynamic_lds.find(fn);
@@ -224,21 +335,21 @@ struct Checker {
         l.n_streams = n;
         const bool encode = l.kernel.find("lit_model_encode_kernel") != std::string::npos, replay = l.kernel.find("row_replay") != std::string::npos;
         if (l.block != (uint32_t)LIT_THREADS) bad("block", "the streaming kernels run 256 threads");
-        need("blob", b.blob, (uint64_t)b.geom.mix_off + 8192u);
+        ro("blob", b.blob, (uint64_t)b.geom.mix_off + 8192u);
         tables(b);
         if (!replay) need("status", b.status, 4);
         ranges("in", b.in, b.in_offsets, b.in_sizes, n, b.stream_len);
         if (!b.in_offsets && !encode && !replay) bad("in_offsets", "the decoders take coded streams by offset and size");
         if (encode) need("sf", b.sf, (uint64_t)n * 2u * b.max_stream_len * 4u);
-        else if (!replay) ranges("out", b.out, b.out_offsets, b.out_sizes, n, b.stream_len);
+        else if (!replay) ranges("out", b.out, b.out_offsets, b.out_sizes, n, b.stream_len, false, true);
         need("stream_bad", b.stream_bad, n, true);
-        need("byte_rank", b.byte_rank, 256, true);
+        ro("byte_rank", b.byte_rank, 256, true);
         need("consumed", b.consumed, (uint64_t)n * 4u, true);
         if (b.resume || b.wstate) need("wstate", b.wstate, 24);
         seg_list(b.seg_begin, b.segs, n, "seg_begin", "segs", sizeof(LitSegment));
         if (cl) {
             seg_list(cl->cmd_begin, cl->cmds, n, "cmd_begin", "cmds", sizeof(LitCommand));
-            need("lit_sizes", cl->lit_sizes, (uint64_t)n * 4u);
+            ro("lit_sizes", cl->lit_sizes, (uint64_t)n * 4u);
             ranges("ins", cl->ins, cl->ins_offsets, cl->ins_sizes, n, 0, true);
             ranges("hist", cl->hist, cl->hist_offsets, cl->hist_sizes, n, 0, true);
         }
@@ -247,8 +358,8 @@ struct Checker {
         const uint32_t n = b.n_streams;
         l.n_streams = n;
         if (b.sf_stride % 4u) bad("sf_stride", "not a multiple of 4");
-        need("sf", b.sf, (uint64_t)n * b.sf_stride * 4u);
-        need("in_sizes", b.in_sizes, (uint64_t)n * 4u, true);
+        ro("sf", b.sf, (uint64_t)n * b.sf_stride * 4u);
+        ro("in_sizes", b.in_sizes, (uint64_t)n * 4u, true);
         need("out", b.out, (uint64_t)n * b.out_slot);
         need("out_offsets", b.out_offsets, (uint64_t)n * 8u);
         need("out_sizes", b.out_sizes, (uint64_t)n * 4u);
@@ -286,7 +397,7 @@ struct Checker {
         const bool one_model = b.xs[1] == nullptr;      // the context-keyed one-model pass: byte payloads, one plane
         need("sf", b.sf, n * b.sf_stride * 4u);
         need("status", b.status, 4);
-        need("blob", b.blob, 256u + 2048u * (uint64_t)std::max(b.n_btypes, 1u));
+        ro("blob", b.blob, 256u + 2048u * (uint64_t)std::max(b.n_btypes, 1u));
         need("sorted", b.sorted, n * b.slot * (one_model ? 1u : 2u));
         need("xs[0]", b.xs[0], n * b.pos_stride * 8u);
         if (!one_model) {
@@ -338,12 +449,16 @@ void check_launch(fakehip::Launch& l, const void* fn, void** args) {
     } else if (has(k, "scan_sizes_kernel")) {
         const uint32_t n = *(const uint32_t*)args[1];
         l.n_streams = n; c.lds_rules(fn, false);
-        c.need("sizes", *(const void**)args[0], (uint64_t)n * 4u); c.need("offsets", *(const void**)args[2], (uint64_t)n * 8u); c.need("total", *(const void**)args[3], 8);
+        const fakehip::ScanArgs sa = {*(const uint32_t**)args[0], n, *(uint64_t**)args[2], *(uint64_t**)args[3], *(const int*)args[4]};
+        keep(&sa, sizeof(sa));
+        c.ro("sizes", *(const void**)args[0], (uint64_t)n * 4u); c.need("offsets", *(const void**)args[2], (uint64_t)n * 8u); c.need("total", *(const void**)args[3], 8);
     } else if (has(k, "pack_copy_kernel")) {
         const uint32_t n = *(const uint32_t*)args[3];
         l.n_streams = n; c.lds_rules(fn, false);
+        const fakehip::PackArgs pa = {*(const uint8_t**)args[0], *(const uint64_t**)args[1], *(const uint32_t**)args[2], n, *(uint8_t**)args[4], *(const uint64_t**)args[5], *(const uint64_t*)args[6], *(uint32_t**)args[7]};
+        keep(&pa, sizeof(pa));
         c.ranges("slots", *(const uint8_t**)args[0], *(const uint64_t**)args[1], *(const uint32_t**)args[2], n, 0);
-        c.need("packed", *(const void**)args[4], 1); c.need("dst_off", *(const void**)args[5], (uint64_t)n * 8u); c.need("status", *(const void**)args[7], 4, true);
+        c.need("packed", *(const void**)args[4], 1); c.ro("dst_off", *(const void**)args[5], (uint64_t)n * 8u); c.need("status", *(const void**)args[7], 4, true);
     } else if (has(k, "learn_byte_rank_kernel")) {
         const uint32_t n = *(const uint32_t*)args[3];
         l.n_streams = n; c.lds_rules(fn, false);
@@ -383,6 +498,14 @@ void set_case(const char* label) { g_case = label; }
 void open_trace(const char* path) { g_trace = fopen(path, "w"); if (!g_trace) { perror(path); abort(); } }
 void trace_note(const std::string& body) { if (g_trace) fprintf(g_trace, "{\"note\": true, \"case\": \"%s\", %s}\n", g_case.c_str(), body.c_str()); }
 const std::vector<Launch>& launches() { return g_launches; }
+int stream_kind(void* stream) { LOCK; auto it = g_streams.find(stream); return it == g_streams.end() ? (stream ? -1 : (int)STREAM_NULL) : it->second.kind; }
+size_t pending_entries(void* stream) { LOCK; size_t n = 0; for (const Op& p : g_pending) n += p.stream == stream; return n; }
+void allow_unordered(const void* inside_range, const char* why) {
+    LOCK;
+    Range* r = range_of((uintptr_t)inside_range);
+    if (!r) violation("(driver)", "allow_unordered", "the address lies in no ledger range");
+    g_unordered_ok.emplace_back(r->born, why);
+}
 uint64_t stream_syncs() { return g_stream_syncs; }
 uint64_t count_calls(const char* function) { return g_calls[function]; }
 std::vector<LedgerEntry> ledger() {
@@ -408,7 +531,6 @@ void check_clean_end() {
 }  // namespace fakehip
 
 // ---- the runtime ---------------------------------------------------------------------------------------------------------------
-#define LOCK std::lock_guard<std::recursive_mutex> lock_(g_mu)
 
 extern "C" {
 
@@ -460,7 +582,7 @@ hipError_t hipMalloc(void** p, size_t bytes) {
     return e;
 }
 hipError_t hipExtMallocWithFlags(void** p, size_t bytes, unsigned) { LOCK; count("hipExtMallocWithFlags"); return new_block(p, bytes, fakehip::KIND_BLOCK); }
-hipError_t hipFree(void* p) { LOCK; count("hipFree"); return free_block(p, "hipFree", fakehip::KIND_BLOCK); }
+hipError_t hipFree(void* p) { LOCK; count("hipFree"); return free_block(p, "hipFree", fakehip::KIND_BLOCK); }      // completes nothing: a free under a launch stays a violation
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { LOCK; count("hipHostMalloc"); return new_block(p, bytes, fakehip::KIND_HOST); }
 hipError_t hipHostFree(void* p) { LOCK; count("hipHostFree"); return free_block(p, "hipHostFree", fakehip::KIND_HOST); }
 
@@ -509,6 +631,7 @@ hipError_t hipMemMap(void* p, size_t bytes, size_t offset, hipMemGenericAllocati
     auto ph = g_phys.find((uint64_t)(uintptr_t)h);
     if (!r || r->kind != fakehip::KIND_RESERVED || ph == g_phys.end() || offset != 0 || bytes != ph->second.bytes || (uintptr_t)p + bytes > r->base + r->bytes) return hipErrorInvalidValue;
     if (r->sealed && !r->maps.empty()) fakehip::violation("(runtime)", "hipMemMap", "a chunk is mapped into a range while part of an earlier mapping is still there");
+    { std::string who; if (any_in_flight_on(r->born, &who)) fakehip::violation(who, "order", "hipMemMap into a range that entry still references (nothing has waited for it)"); }
     const size_t off = (uintptr_t)p - r->base;
     for (const Mapping& m : r->maps) if (off < m.off + m.bytes && m.off < off + bytes) fakehip::violation("(runtime)", "hipMemMap", "the addresses are mapped already");
     r->sealed = false;
@@ -557,42 +680,97 @@ static void check_device_side(const char* fn, const char* field, const void* p, 
     if (!r) return;     // ordinary host memory
     if (have < bytes) fakehip::violation(fn, field, "needs " + std::to_string(bytes) + " bytes, the live extent from there holds " + std::to_string(have));
 }
-static hipError_t copy_impl(const char* fn, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, bool sync) {
+namespace {
+void span_of(std::vector<fakehip::Span>& out, const void* p, size_t bytes, bool write) {
+    if (bytes == 0) return;
+    Range* r = range_of((uintptr_t)p);
+    if (r) out.push_back({r->born, (uintptr_t)p, (uintptr_t)p + bytes, write});
+}
+bool device_side(const void* p) { Range* r = range_of((uintptr_t)p); return r && r->kind != fakehip::KIND_HOST; }
+}
+// One copy of `height` rows of `width` bytes.  sync: hipMemcpy (waits for the null stream and the blocking ones; an entry of a
+// non-blocking stream that touches the same bytes is an `order` violation).  Otherwise an entry of `stream`'s queue: device memory
+// is written at once, in program order; on a non-blocking stream a destination in host memory receives the bytes -- as they are
+// at this place of the queue -- when the entry completes, and a page-locked source must keep its bytes until then.
+static hipError_t copy_rows(const char* fn, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, bool sync, hipStream_t stream) {
     LOCK; count(fn);
-    check_device_side(fn, "dst", dst, bytes); check_device_side(fn, "src", src, bytes);
-    if (kind != hipMemcpyDeviceToDevice || bytes <= kCopyLimit) std::memmove(dst, src, bytes);
-    if (sync) complete(nullptr, ~0ull, true);
+    if (width == 0 || height == 0) return hipSuccess;
+    const size_t dbytes = (height - 1) * dpitch + width, sbytes = (height - 1) * spitch + width;
+    check_device_side(fn, "dst", dst, dbytes); check_device_side(fn, "src", src, sbytes);
+    Op op; op.stream = stream; op.type = OP_COPY; op.what = fn;
+    span_of(op.spans, dst, dbytes, true); span_of(op.spans, src, sbytes, false);
+    const bool carry = kind != hipMemcpyDeviceToDevice || width * height <= kCopyLimit;
+    auto carry_out = [&]() { if (carry) for (size_t i = 0; i < height; ++i) std::memmove((uint8_t*)dst + i * dpitch, (const uint8_t*)src + i * spitch, width); };
+    if (sync) {
+        check_order(fn, nullptr, true, Clock(), op.spans);
+        complete_legacy();
+        carry_out();
+        return hipSuccess;
+    }
+    const bool non_blocking = stream_state(stream).kind == fakehip::STREAM_NON_BLOCKING;
+    if (non_blocking && !device_side(dst)) {
+        op.deferred = true; op.dst = dst; op.dpitch = dpitch; op.width = width; op.height = height;
+        op.staged.resize(width * height);
+        for (size_t i = 0; i < height; ++i) std::memcpy(op.staged.data() + i * width, (const uint8_t*)src + i * spitch, width);
+    } else carry_out();
+    Range* sr = range_of((uintptr_t)src);
+    if (non_blocking && sr && sr->kind == fakehip::KIND_HOST && height == 1 && width <= kCopyLimit) { op.pinned_src = src; op.pinned_copy.assign((const uint8_t*)src, (const uint8_t*)src + width); }
+    enqueue(std::move(op));
     return hipSuccess;
 }
-hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { return copy_impl("hipMemcpy", dst, src, bytes, kind, true); }
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t) { return copy_impl("hipMemcpyAsync", dst, src, bytes, kind, false); }
-hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t) {
-    LOCK; count("hipMemcpy2DAsync");
-    if (height == 0 || width == 0) return hipSuccess;
-    if (width > dpitch || width > spitch) return hipErrorInvalidPitchValue;
-    check_device_side("hipMemcpy2DAsync", "dst", dst, (height - 1) * dpitch + width);
-    check_device_side("hipMemcpy2DAsync", "src", src, (height - 1) * spitch + width);
-    if (height * width <= kCopyLimit) for (size_t i = 0; i < height; ++i) std::memmove((uint8_t*)dst + i * dpitch, (const uint8_t*)src + i * spitch, width);
-    return hipSuccess;
+hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { return copy_rows("hipMemcpy", dst, bytes, src, bytes, bytes, 1, kind, true, nullptr); }
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) { return copy_rows("hipMemcpyAsync", dst, bytes, src, bytes, bytes, 1, kind, false, s); }
+hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, hipStream_t s) {
+    if (height == 0 || width == 0) { LOCK; count("hipMemcpy2DAsync"); return hipSuccess; }
+    if (width > dpitch || width > spitch) { LOCK; count("hipMemcpy2DAsync"); return hipErrorInvalidPitchValue; }
+    return copy_rows("hipMemcpy2DAsync", dst, dpitch, src, spitch, width, height, kind, false, s);
 }
-static hipError_t fill_impl(const char* fn, void* p, int v, size_t bytes, bool sync) {
+static hipError_t fill_impl(const char* fn, void* p, int v, size_t bytes, bool sync, hipStream_t stream) {
     LOCK; count(fn);
     check_device_side(fn, "dst", p, bytes);
+    Op op; op.stream = stream; op.type = OP_FILL; op.what = fn;
+    span_of(op.spans, p, bytes, true);
+    if (sync) { check_order(fn, nullptr, true, Clock(), op.spans); complete_legacy(); }
     if (v == 0 && bytes >= ((size_t)1 << 20)) {      // whole pages go back to the zero page, the ends are written
         const uintptr_t a = (uintptr_t)p, lo = (a + kPage - 1) / kPage * kPage, hi = (a + bytes) / kPage * kPage;
         std::memset(p, 0, lo - a); madvise((void*)lo, hi - lo, MADV_DONTNEED); std::memset((void*)hi, 0, a + bytes - hi);
     } else std::memset(p, v, bytes);
-    if (sync) complete(nullptr, ~0ull, true);
+    if (!sync) enqueue(std::move(op));
     return hipSuccess;
 }
-hipError_t hipMemset(void* p, int v, size_t bytes) { return fill_impl("hipMemset", p, v, bytes, true); }
-hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t) { return fill_impl("hipMemsetAsync", p, v, bytes, false); }
+hipError_t hipMemset(void* p, int v, size_t bytes) { return fill_impl("hipMemset", p, v, bytes, true, nullptr); }
+hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t s) { return fill_impl("hipMemsetAsync", p, v, bytes, false, s); }
 
 // ---- streams and events
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { LOCK; count("hipStreamCreateWithFlags"); *s = (hipStream_t) new int(0); return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { LOCK; count("hipStreamDestroy"); delete (int*)s; return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t s) { LOCK; count("hipStreamSynchronize"); ++g_stream_syncs; complete(s, ~0ull, false); return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { LOCK; count("hipStreamWaitEvent"); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) {
+    LOCK; count("hipStreamCreateWithFlags");
+    *s = (hipStream_t) new int(0);
+    StreamState st; st.kind = (flags & hipStreamNonBlocking) ? fakehip::STREAM_NON_BLOCKING : fakehip::STREAM_BLOCKING;
+    g_streams[(void*)*s] = st;
+    return hipSuccess;
+}
+hipError_t hipStreamCreate(hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamDefault); }
+hipError_t hipStreamGetFlags(hipStream_t s, unsigned* flags) { LOCK; count("hipStreamGetFlags"); *flags = stream_state(s).kind == fakehip::STREAM_NON_BLOCKING ? hipStreamNonBlocking : hipStreamDefault; return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) {      // the real call lets the queue run out and returns at once; nobody can name the stream afterwards, so the queue is completed here
+    LOCK; count("hipStreamDestroy");
+    if (!s || !g_streams.count((void*)s)) fakehip::violation("(runtime)", "hipStreamDestroy", "not a live stream");
+    complete_stream(s, ~0ull);
+    g_streams.erase((void*)s);
+    delete (int*)s;
+    return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s) { LOCK; count("hipStreamSynchronize"); ++g_stream_syncs; (void)stream_state(s); complete_stream(s, ~0ull); return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { LOCK; count("hipDeviceSynchronize"); complete_where([](const Op&) { return true; }); return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    LOCK; count("hipStreamWaitEvent");
+    Event* ev = (Event*)e;
+    if (!ev->recorded) return hipSuccess;      // as the real call: an event never recorded orders nothing
+    StreamState& st = stream_state(s);
+    merge(st.clock, ev->clock);
+    Op op; op.stream = s; op.type = OP_WAIT; op.what = "hipStreamWaitEvent";
+    enqueue(std::move(op));
+    return hipSuccess;
+}
 hipError_t hipEventCreate(hipEvent_t* e) { LOCK; count("hipEventCreate"); *e = (hipEvent_t) new Event(); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { LOCK; count("hipEventDestroy"); delete (Event*)e; return hipSuccess; }
@@ -600,14 +778,23 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     LOCK; hipError_t err;
     if (injected("hipEventRecord", &err)) { g_last_error = err; return err; }
     Event* ev = (Event*)e;
+    Op op; op.stream = s; op.type = OP_RECORD; op.what = "hipEventRecord";
+    const Op& q = enqueue(std::move(op));
     ev->stream = s; ev->recorded = true; ev->seq = g_launches.size();      // behind every launch made so far
+    ev->id = q.id; ev->clock = q.clock; merge(ev->clock, s, q.id);
     return hipSuccess;
 }
 hipError_t hipEventSynchronize(hipEvent_t e) {
     LOCK; hipError_t err;
     if (injected("hipEventSynchronize", &err)) { g_last_error = err; return err; }
     Event* ev = (Event*)e;
-    if (ev->recorded) complete(ev->stream, ev->seq, false);
+    if (ev->recorded) complete_stream(ev->stream, ev->id);
+    return hipSuccess;
+}
+hipError_t hipEventQuery(hipEvent_t e) {
+    LOCK; count("hipEventQuery");
+    Event* ev = (Event*)e;
+    if (ev->recorded) for (const Op& p : g_pending) if (p.stream == ev->stream && p.id <= ev->id) return hipErrorNotReady;
     return hipSuccess;
 }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
@@ -623,7 +810,6 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     *ms = t;
     return hipSuccess;
 }
-
 // ---- launches
 hipError_t hipFuncSetAttribute(const void* fn, hipFuncAttribute attr, int value) {
     LOCK; count("hipFuncSetAttribute");
@@ -640,7 +826,12 @@ hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, s
     l.seq = g_launches.size() + 1; l.kernel = it->second; l.label = g_case;
     l.grid = grid.x; l.block = block.x; l.lds = (uint32_t)lds; l.stream = stream; l.in_flight = true;
     l.n_streams = 0; l.tables = 0; l.tables_kind = -1; l.tables_born = 0;
+    (void)stream_state(stream);
     check_launch(l, fn, args);
+    {
+        Op op; op.stream = stream; op.type = OP_LAUNCH; op.what = l.kernel; op.launch_seq = l.seq; op.spans = l.spans;
+        enqueue(std::move(op));
+    }
     float ms = 1.f;
     for (auto& s : g_scripts) if (!s.second.empty() && has(l.kernel, s.first.c_str())) { ms = s.second.front(); s.second.pop_front(); break; }
     g_durations.push_back(ms);

@@ -20,6 +20,10 @@ struct LedgerEntry {
     uint64_t born;             // allocation order
 };
 
+// one stretch of a ledger range a queued entry touches: `born` names the range, [lo, hi) the addresses, `write` is false only where
+// the argument struct declares the pointer const (or the entry is a copy's source)
+struct Span { uint64_t born; uintptr_t lo, hi; bool write; };
+
 struct Launch {
     uint64_t seq;              // 1, 2, ... over the process
     std::string kernel;        // demangled
@@ -31,7 +35,12 @@ struct Launch {
     uintptr_t tables; int tables_kind; uint64_t tables_born;     // LitBatch kernels: where the tables lie (Kind), which allocation
     std::vector<uint64_t> refs;                                  // `born` of every ledger entry a pointer of the arguments lies in
     std::vector<uint8_t> args;                                   // the first by-value struct, copied
+    std::vector<Span> spans;                                     // what the `order` rule compares: every checked pointer with its extent
 };
+
+// what Launch::args holds for the two kernels of the pack pass, which take plain arguments and no struct
+struct ScanArgs { const uint32_t* sizes; uint32_t n; uint64_t* offsets; uint64_t* total; int accumulate; };
+struct PackArgs { const uint8_t* slots; const uint64_t* src_off; const uint32_t* sizes; uint32_t n; uint8_t* packed; const uint64_t* dst_off; uint64_t cap; uint32_t* status; };
 
 // ---- the device --------------------------------------------------------------------------------------------------------------
 void set_capacity(size_t bytes);             // device memory; hipMalloc / hipMemCreate fail beyond it, hipMemGetInfo answers from it
@@ -65,6 +74,11 @@ void open_trace(const char* path);           // JSON lines, one per launch and o
 void trace_note(const std::string& json_object_body);      // {"note": true, <body>}
 const std::vector<Launch>& launches();
 std::vector<LedgerEntry> ledger();
+enum StreamKind : int { STREAM_NULL = 0, STREAM_BLOCKING = 1, STREAM_NON_BLOCKING = 2 };
+int stream_kind(void* stream);               // -1: not a live stream
+size_t pending_entries(void* stream);        // queued entries of one stream nothing has completed yet
+// `order` allow-list: a ledger range (named by any address inside it) that streams may share without an edge (tests/c/README.md)
+void allow_unordered(const void* inside_range, const char* why);
 uint64_t stream_syncs();                     // hipStreamSynchronize calls so far
 uint64_t count_calls(const char* function);  // calls of one runtime function so far
 void check_clean_end();                      // aborts unless the ledger holds no live block, chunk or pinned host buffer

@@ -125,7 +125,8 @@ def find_hipcc():
 def build_capi_contract(csrc=None, tag="contract"):
     """tests/c/_build/capi_contract: divans_amd/csrc/capi.cpp and the six .hip files compiled for the HOST only (hipcc
     --offload-host-only: the launchers and kernel stubs, no device code), tests/c/fakehip_rt.cpp in place of libamdhip64 and the
-    driver tests/c/capi_contract.cpp, everything under -fsanitize=address,undefined.  A stand-alone program: nothing is preloaded.
+    driver tests/c/capi_contract.cpp (scenarios on the null stream, and streams_* on a caller's non-blocking stream: tests/c/README.md,
+    "The stream model"), everything under -fsanitize=address,undefined.  A stand-alone program: nothing is preloaded.
     `csrc` selects another copy of the product sources (a copy with a deliberate break, to see a contract check fire)."""
     from concurrent.futures import ThreadPoolExecutor
     hipcc, clang = find_hipcc()

@@ -119,6 +119,9 @@ def _cut(n, cuts):
     return [b - a for a, b in zip(edges[:-1], edges[1:])]
 
 
+Data, cut = _Data, _cut      # public names: tests/caller_stream_cases.py builds its batches with them
+
+
 def shapes(fam, sources, small=False):
     """[(name, literal bytes, segment list)] of a family: S0..S7 and the random fill, N_STREAMS in all (small: S1-S5 and S7 at the
     lengths the pure-Python restatement can afford, every phase change of the full shapes kept but the chunk seam)"""
