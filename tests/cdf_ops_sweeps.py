@@ -551,3 +551,63 @@ def compare(impl, ops, got, exp, what=""):
         op = tuple(int(v) for v in ops[k])
         raise AssertionError(f"{what}: implementation {impl} = {IMPL_NAMES[impl]}, op index {k}, op {op} ({OP_NAMES.get(op[0], '?')}): "
                              f"got {got[k].tolist()}, expected {exp[k].tolist()}; {bad.size} of {len(ops)} records differ")
+
+
+# ---- the scripts of the reference's own unit tests (tests/test_gpu_reference_unit_tests.py runs them on the device, tests/test_cdf_ops_oracle_cpu.py on both CPU opinions)
+MED, SLOW = (0x30, 0x4000), (0x20, 0x1000)
+BUF0 = [0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 5, 5, 5, 5, 5, 6, 7, 8, 8, 9, 9, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 11, 12, 12, 12, 13, 13, 13, 14, 15,
+        15, 15, 15, 15, 15, 15]
+BUF1 = [0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 5, 5, 5, 5, 5]
+
+
+def script_operation_test_helper():
+    Q = 1 << 15
+    ops = []
+    for s in [3, 3, 9, 14, 0, 15, 7, 7, 7, 2] * 3:       # give row 1 a shape of its own (the reference leaves it at the default)
+        ops.append((1, s, *SLOW))
+    for s in BUF0:
+        ops.append((0, s, *MED))
+    ops.append((2, Q >> 2, 0, 0))
+    for s in BUF1:
+        ops.append((7, s, *MED))                          # the pipelined kernels' blend variant must agree too
+    for rate in (Q >> 2, Q >> 1, (Q >> 1) + (Q >> 2), 0, Q):
+        ops.append((2, rate, 0, 0))
+    return ops
+
+
+def script_declare_common_tests():
+    ops = [(0, (i * 7 + 3) & 15, *MED) for i in range(100)]
+    ops += [(3, s, 0, 0) for s in range(16)]
+    ops += [(4, off, 0, 0) for off in range(0, 1 << 15, 1)]
+    return ops
+
+
+def script_lcg_sample_run():
+    # simple_rand, common_tests.rs:44-48 (seed 1): x = x * 1103515245 + 12345; symbols drawn from a fixed pdf through a prefix table
+    x = 1
+    pdf = [0.1, 0.01, 0.03, 0.2, 0.02, 0.05, 0.04, 0.15, 0.01, 0.06, 0.03, 0.07, 0.02, 0.1, 0.08, 0.03]
+    edges = np.cumsum(pdf)
+    ops = []
+    for _ in range(60000):
+        x = (x * 1103515245 + 12345) & 0xFFFFFFFF
+        u = ((x >> 16) & 0x7FFF) / 32768.0
+        ops.append((0, int(np.searchsorted(edges, u, side="right").clip(0, 15)), *MED))
+    ops += [(0, 15, *MED)] * 30000                         # common_tests.rs:94-103
+    return ops
+
+
+def script_weights_update_sequences():
+    rng = np.random.default_rng(7)
+    ops = []
+    for k in range(30000):
+        if k % 5000 == 0:
+            ops.append((6, 0, 0, 0))
+        mode = (k // 5000) % 3
+        if mode == 0:
+            p0, p1, pm = (int(v) for v in rng.integers(1, 32767, size=3))
+        elif mode == 1:                                    # one model much better than the other: drives the weights to the 2^24 normalisation
+            p0, p1 = int(rng.integers(20000, 32767)), int(rng.integers(1, 300)); pm = int(rng.integers(1000, 30000))
+        else:
+            p0 = p1 = pm = int(rng.integers(1, 32767))
+        ops.append((5, p0, p1, pm))
+    return ops

@@ -27,6 +27,12 @@ def bind(L):
     return L
 
 
+def product_library():
+    """the product (divans_amd/libdivans_hip.so) with the per-stream C ABI bound: what the GPU tests pass as `L`"""
+    import divans_amd as da
+    return bind(da.load_library())
+
+
 def ffi_compress(L, data, options, buf_size=65536, feed=None, trace=None):
     """c/example.c's loop, once per piece of `feed` bytes of input (default: one piece = everything): divans_encode is called with
     what is left of the piece and an empty buffer until the piece is taken.  `trace` collects the bytes every encode call returned."""

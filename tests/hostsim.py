@@ -161,3 +161,26 @@ def build_capi_contract(csrc=None, tag="contract"):
     if _newer(exe, objs + [stub]):
         subprocess.run([clang] + san + ["-g", "-o", exe, "-x", "c", stub, "-x", "none"] + objs + ["-lpthread"], check=True)
     return exe
+
+
+# ---- the launch trace the program writes ------------------------------------------------------------------------------------------
+LAUNCH_TRACE_GOLDEN = os.path.join(ROOT, "tests", "golden", "launch_trace_small.json")
+
+
+def trace_notes(trace, entry=None):
+    return [r for r in trace if r.get("note") and (entry is None or r.get("entry") == entry)]
+
+
+def small_trace_summary(trace):
+    """what tests/golden/launch_trace_small.json holds: per codec and batch shape, the decode kernel, grid and LDS of decode_batch and
+    decode_segments_batch, what divans_gpu_codec_info reports of the grid, and the pass every encode call ran"""
+    out = {}
+    for r in trace_notes(trace):
+        case = r["case"]
+        if r["entry"] in ("decode_batch", "decode_segments_batch"):
+            out.setdefault(case, {})[r["entry"]] = {"kernel": r["kernel"], "grid": r["grid"]}
+        elif r["entry"] == "info":
+            out.setdefault(case, {})["info"] = {k: r[k] for k in ("n_streams", "resident_groups", "blocks", "rows_per_stream")}
+        elif r["entry"] in ("encode_batch", "encode_segments_batch"):
+            out.setdefault(case, {})[r["entry"]] = r["ran"]
+    return out

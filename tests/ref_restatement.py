@@ -330,3 +330,33 @@ def encode_stream(cfg, data):
 def decode_stream(cfg, coded, n):
     lc = LiteralCoder(**cfg)
     return lc.code_bytes(None, n, dec=AnsDecoder(coded))
+
+
+# ---- a segment driver over the restatement, for the CPU-tier tests that guard the oracle's (tests/test_*_cases_cpu.py)
+def to_rr(cfg):
+    return dict(context_map=bytes(cfg.literal_context_map), mixing_mask=bytes(cfg.mixing_mask), prediction_mode=cfg.prediction_mode,
+                btype=cfg.btype, mixing_param=cfg.context_mixing, speeds=[(s.inc, s.lim) for s in cfg.literal_adaptation])
+
+
+def rr_segments_encode(cfg, lit, segs):
+    """codec/mod.rs:711-792 over the restatement: block type and last_8_literals per Literal command, one LIT coder for the stream"""
+    lc = LiteralCoder(**to_rr(cfg))
+    enc = AnsEncoder()
+    pos = 0
+    for n, bt, l8 in zip(segs["len"].tolist(), segs["btype"].tolist(), segs["last8"].tolist()):
+        lc.btype, lc.last_8 = bt, l8
+        lc.code_bytes(bytes(lit[pos:pos + n]), n, enc=enc)
+        pos += n
+    assert pos == lit.size
+    enc.flush_chunk()
+    return bytes(enc.out)
+
+
+def rr_segments_decode(cfg, coded, segs):
+    lc = LiteralCoder(**to_rr(cfg))
+    dec = AnsDecoder(coded)
+    out = b""
+    for n, bt, l8 in zip(segs["len"].tolist(), segs["btype"].tolist(), segs["last8"].tolist()):
+        lc.btype, lc.last_8 = bt, l8
+        out += lc.code_bytes(None, n, dec=dec)
+    return out

@@ -88,6 +88,8 @@ def families():
 
 
 FAMILIES = families()
+# (family, speed whose row totals leave i16): the launches the library checks for wrapped rows, generation 1 without a cache
+WRAP_CASES = [("mm4_map_plain", (0x3000, 0x1000)), ("mmx_map_plain", (8180, 64)), ("mm4_const_plain", (0x7800, 0x7800))]
 
 
 class _Data:

@@ -8,7 +8,7 @@ import pytest
 import bucketed_segment_cases as bc
 import pyoracle as po
 import segment_cases as sc
-from test_segment_cases_cpu import rr_segments_decode, rr_segments_encode
+from ref_restatement import rr_segments_decode, rr_segments_encode
 
 _BATCHES = {}
 

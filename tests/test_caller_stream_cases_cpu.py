@@ -10,7 +10,7 @@ import caller_stream_cases as cs
 import pyoracle as po
 import segment_cases as sc
 import stride_bucketed_cases as st
-from test_segment_cases_cpu import rr_segments_decode, rr_segments_encode
+from ref_restatement import rr_segments_decode, rr_segments_encode
 
 KEYS = list(cs.FAMILIES)
 

@@ -15,8 +15,9 @@ import subprocess
 
 import pytest
 
+import encode_dispatch_cases as ed
 import hostsim
-import test_capi_launch_contract_cpu as base
+import pyoracle as po
 
 pytestmark = pytest.mark.skipif(hostsim.find_hipcc()[0] is None, reason="hipcc is not installed: the product's host code cannot be compiled")
 
@@ -26,7 +27,7 @@ def program(tmp_path_factory):
     exe = hostsim.build_capi_contract()
     d = tmp_path_factory.mktemp("caller_streams")
     configs = d / "configs.bin"
-    configs.write_bytes(base.config_records())
+    configs.write_bytes(ed.config_records(po))
 
     def run(scenario):
         trace = d / (scenario + ".jsonl")
@@ -46,7 +47,7 @@ def test_every_entry_point_on_a_non_blocking_stream(program):
     flags), pack_streams, and every setter called behind launches nothing has waited for.  The dispatch does not depend on the
     stream: the trace's summary is the committed one of the null stream."""
     trace = program("streams_small")
-    assert base.small_trace_summary(trace) == json.load(open(base.GOLDEN))
+    assert hostsim.small_trace_summary(trace) == json.load(open(hostsim.LAUNCH_TRACE_GOLDEN))
     cases = {r["case"] for r in trace if "seq" in r}
     for name in ("simple", "mixing", "context_keyed"):
         assert f"{name}/setters_in_flight" in cases

@@ -7,33 +7,17 @@ A contract violation aborts the program with "CONTRACT VIOLATION ... kernel <nam
 driver exits with "EXPECTATION FAILED"; either fails the test with the message."""
 import json
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import encode_dispatch_cases as ed
 import far_offset_cases as fo
 import hostsim
 import pyoracle as po
-import test_gpu_encode_dispatch as ed
 
 pytestmark = pytest.mark.skipif(hostsim.find_hipcc()[0] is None, reason="hipcc is not installed: the product's host code cannot be compiled")
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_trace_small.json")
-NONE = 0xFFFFFFFF
-
-
-def config_records():
-    """the ten codecs of tests/test_gpu_encode_dispatch.py's table, as the driver reads them (the oracle's configuration structs have
-    the product's bytes: Family.pair asserts it wherever both exist)"""
-    out = b""
-    for key, row in ed.TABLE.items():
-        o = row.family.configure(getattr(po, "config_" + row.family.base)())
-        if row.wrap:
-            for i in range(4):
-                o.literal_adaptation[i].inc, o.literal_adaptation[i].lim = ed.WRAP_SPEED
-        out += struct.pack("<32sIIII", key.encode(), NONE if row.types is None else row.types, int(row.path_2_before_types), int(row.family.btype), 0) + bytes(o)
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -41,7 +25,7 @@ def program(tmp_path_factory):
     exe = hostsim.build_capi_contract()
     d = tmp_path_factory.mktemp("capi_contract")
     configs = d / "configs.bin"
-    configs.write_bytes(config_records())
+    configs.write_bytes(ed.config_records(po))
     sizes = d / "sizes.bin"
     sizes.write_bytes(np.array([fo.WORK_LENGTHS[i % len(fo.WORK_LENGTHS)] for i in range(fo.WORK_STREAMS)], np.uint32).tobytes())
 
@@ -56,32 +40,13 @@ def program(tmp_path_factory):
     return run
 
 
-def _notes(trace, entry=None):
-    return [r for r in trace if r.get("note") and (entry is None or r.get("entry") == entry)]
-
-
-def small_trace_summary(trace):
-    """what tests/golden/launch_trace_small.json holds: per codec and batch shape, the decode kernel, grid and LDS of decode_batch and
-    decode_segments_batch, what divans_gpu_codec_info reports of the grid, and the pass every encode call ran"""
-    out = {}
-    for r in _notes(trace):
-        case = r["case"]
-        if r["entry"] in ("decode_batch", "decode_segments_batch"):
-            out.setdefault(case, {})[r["entry"]] = {"kernel": r["kernel"], "grid": r["grid"]}
-        elif r["entry"] == "info":
-            out.setdefault(case, {})["info"] = {k: r[k] for k in ("n_streams", "resident_groups", "blocks", "rows_per_stream")}
-        elif r["entry"] in ("encode_batch", "encode_segments_batch"):
-            out.setdefault(case, {})[r["entry"]] = r["ran"]
-    return out
-
-
 @pytest.fixture(scope="module")
 def small(program):
     return program("small")
 
 
 def test_every_entry_point_at_small_shapes(small):
-    """scenario 1: the contract held at every launch (the program ended well); the pass of every encode call is the dispatch table's"""
+    """scenario 1: the contract held at every launch (the program ended well); the pass of every encode call is the dispatch table's (tests/encode_dispatch_cases.py)"""
     launches = [r for r in small if "seq" in r]
     kernels = {r["kernel"].split("<")[0] for r in launches}
     for family in ("lit_model_encode_kernel", "lit_decode2_kernel_any", "lit_decode_kernel", "lit_decode2_cmd_kernel", "lit_decode2_cmd_hist_kernel", "rans_encode",
@@ -92,7 +57,7 @@ def test_every_entry_point_at_small_shapes(small):
         for shape in ("ragged37", "full_grid"):
             for path in (0, 1, 2):
                 case = f"{key}/{shape}/path{path}"
-                notes = [r for r in _notes(small) if r["case"] == case]
+                notes = [r for r in hostsim.trace_notes(small) if r["case"] == case]
                 accepted = next(r["accepted"] for r in notes if r["entry"] == "set_encode_path")
                 assert accepted == (path < 2 or row.accepted), case
                 # where path 2 is refused the codec keeps the path it had: 1 in this walk, or the 2 that was accepted before the block types
@@ -101,7 +66,7 @@ def test_every_entry_point_at_small_shapes(small):
                 assert ran["encode_batch"] == no_list and ran["model_batch"] == no_list and ran["encode_packed"] == no_list, (case, ran)
                 assert ran["encode_segments_batch"] == listed, (case, ran)
                 assert ran["encode_commands_batch"] == listed and ran["encode_commands_history_batch"] == listed, (case, ran)
-            dec = {r["entry"]: r for r in _notes(small) if r["case"] == f"{key}/{shape}/decode"}
+            dec = {r["entry"]: r for r in hostsim.trace_notes(small) if r["case"] == f"{key}/{shape}/decode"}
             full = shape == "full_grid"
             if not row.wrap:
                 # one stream more than blocks2 * 16: the codec's own organisation (2-way without mixing) on the whole grid
@@ -117,7 +82,7 @@ def test_every_entry_point_at_small_shapes(small):
 def test_small_trace_is_the_committed_one(small):
     """tests/golden/launch_trace_small.json -- per codec and batch shape the pass of every encode call, the decode kernel and grid, the
     geometry divans_gpu_codec_info reports -- is what the harness gives today: a change of the dispatch has to change the file"""
-    assert small_trace_summary(small) == json.load(open(GOLDEN))
+    assert hostsim.small_trace_summary(small) == json.load(open(hostsim.LAUNCH_TRACE_GOLDEN))
 
 
 def test_open_fault_sequence_replayed(program):
@@ -129,7 +94,7 @@ def test_open_fault_sequence_replayed(program):
     a block candidate and gives its mapped best back, so the pool is empty.  The contract then held at every launch of the sequence:
     the program ended well."""
     trace = program("m6")
-    notes = [r for r in _notes(trace) if r["case"].startswith("m6/work/path1")]
+    notes = [r for r in hostsim.trace_notes(trace) if r["case"].startswith("m6/work/path1")]
     dec = {r["entry"]: r for r in notes if r["entry"].startswith("decode")}
     assert dec["decode_segments_batch"]["kernel"] == "divans_hip::lit_decode2_kernel_any<-1, true, false, true, 17>"
     assert dec["decode_segments_batch"]["lds"] == 27648
@@ -144,7 +109,7 @@ def test_open_fault_sequence_replayed(program):
     assert ran == {"encode_batch": 1, "encode_segments_batch": 1, "model_batch": 1}
     # where the replay differs from what the record supposed
     assert placement["table_bytes"] == 1536 * 16 * 6144 * 32
-    pools = _notes(trace, "pool")
+    pools = hostsim.trace_notes(trace, "pool")
     assert [p["case"].split("/")[0] for p in pools] == ["simple", "mixing", "context_keyed", "m6"] and all(p["idle_ranges"] == 0 for p in pools)
     first_m6_launch = next(r for r in trace if "seq" in r and r["case"].startswith("m6/") and r["tables"] != "none")
     earlier = {r["tables_id"] for r in trace if "seq" in r and not r["case"].startswith("m6/") and r["tables"] != "none"}
@@ -157,7 +122,7 @@ def test_placement_search(program):
     """scenario 3: scripted times; the fastest stays, two copies at most, no wait unless a call of another shape came between, block
     and chunk candidates alternate, the eager form, a candidate whose allocation fails"""
     trace = program("placement")
-    calls = _notes(trace, "search_call")
+    calls = hostsim.trace_notes(trace, "search_call")
     assert [c["tables"] for c in calls] == ["chunks", "block", "chunks", "block", "block", "block"]
     assert max(c["copies"] for c in calls) == 2 and calls[-1]["copies"] == 1
 
@@ -172,7 +137,7 @@ def test_failure_sweep(program):
     a small codec and on one with mapped tables under a placement search; and the case of its own: the launch, or the event record,
     behind placement_step's swap fails and the same shape is called again"""
     trace = program("failures")
-    sweeps = _notes(trace, "sweep")
+    sweeps = hostsim.trace_notes(trace, "sweep")
     assert len(sweeps) == 10
     for s in sweeps:
         # `calls`: the injectable calls of the good run up to the end of its third call.  Every one of them is failed unless they are

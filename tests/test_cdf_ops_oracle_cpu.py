@@ -42,9 +42,8 @@ def test_c_interpreter_agrees_with_the_python_restatement(name):
 
 
 def test_existing_reference_unit_scripts_agree():
-    # the four scripts of tests/test_gpu_reference_unit_tests.py, in full, on both CPU opinions
-    import test_gpu_reference_unit_tests as t
-    for make in (t.script_operation_test_helper, t.script_declare_common_tests, t.script_lcg_sample_run, t.script_weights_update_sequences):
+    # the four scripts tests/test_gpu_reference_unit_tests.py runs on the device, in full, on both CPU opinions
+    for make in (sw.script_operation_test_helper, sw.script_declare_common_tests, sw.script_lcg_sample_run, sw.script_weights_update_sequences):
         sw.second_opinion(make())
 
 

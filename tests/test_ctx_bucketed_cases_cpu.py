@@ -14,7 +14,7 @@ import bucketed_segment_cases as bc
 import ctx_bucketed_cases as cc
 import pyoracle as po
 import segment_cases as sc
-from test_segment_cases_cpu import rr_segments_decode, rr_segments_encode
+from ref_restatement import rr_segments_decode, rr_segments_encode
 
 KEYS = list(cc.FAMILIES)
 

@@ -11,7 +11,8 @@ pytestmark = pytest.mark.gpu
 def test_batch_containers_equal_per_stream_abi_and_oracle(corpus):
     import divans_amd as da
     import workload
-    from test_gpu_ffi import ffi_compress, ffi_decompress
+    import ffi_harness as fh
+    lib = fh.product_library()
     rng = np.random.default_rng(5)
     sizes = [0, 1, 15, 16, 4097, 65536, 70001, 200000] + [int(x) for x in rng.integers(1, 90000, size=24)]
     blocks = workload.make_blocks(corpus, 100, len(sizes), block_len=65536)
@@ -25,11 +26,11 @@ def test_batch_containers_equal_per_stream_abi_and_oracle(corpus):
             ref = po.stream_compress_raw(inputs[i], po.stream_options(call_buffer_size=65536, **orc), call_inputs=[inputs[i].size])
             assert containers[i].size == ref.size and (containers[i] == ref).all(), (i, sizes[i])
         for i in (2, 5, 6, 9):
-            assert (containers[i] == ffi_compress(inputs[i], ffi_opts)).all()
+            assert (containers[i] == fh.ffi_compress(lib, inputs[i], ffi_opts)).all()
         back, t2 = da.batch_decompress(containers, sum(sizes), da.batch_options(host_threads=4))
         for i, x in enumerate(inputs):
             assert back[i].size == x.size and (back[i] == x).all(), i
-        assert (ffi_decompress(containers[7], sizes[7]) == inputs[7]).all()
+        assert (fh.ffi_decompress(lib, containers[7], sizes[7]) == inputs[7]).all()
 
 
 def test_batch_decompress_groups_configurations_and_rejects_damage(corpus):

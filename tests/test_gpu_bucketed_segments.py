@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 
 import bucketed_segment_cases as bc
+import gpu_harness as gh
 import irtext
 import pyoracle as po
 import segment_cases as sc
 
 pytestmark = pytest.mark.gpu
-BAD_SEGMENT = 4
 KEYS = list(bc.CONFIGS)
 _CASES = {}
 
@@ -25,10 +25,6 @@ def sources(corpus, random_then_unicode, shuffle384):
     return (corpus, random_then_unicode, shuffle384)
 
 
-def _oracle(ocfg, streams):
-    return [po.lit_segments_encode(ocfg, lit, segs["len"], segs["btype"], segs["last8"]) for _, lit, segs in streams]
-
-
 def _case(key, sources):
     """the configuration pair, its batch and the oracle's bytes of every stream: computed once, shared, never written to"""
     if key not in _CASES:
@@ -36,44 +32,8 @@ def _case(key, sources):
         fam = bc.CONFIGS[key]
         g, o = fam.pair(da, po)
         streams = bc.batch(fam, sources)
-        _CASES[key] = (fam, g, o, streams, _oracle(o, streams))
+        _CASES[key] = (fam, g, o, streams, gh.oracle_bytes(o, streams))
     return _CASES[key]
-
-
-def _tensors(torch, streams):
-    dev = torch.device("cuda")
-    buf, offs, sizes = bc.layout(streams)
-    segs = np.concatenate([s[2] for s in streams] + [np.zeros(1, sc.SEG_DTYPE)])      # (one spare record: the array is never empty)
-    seg_begin = np.concatenate([[0], np.cumsum([s[2].size for s in streams])]).astype(np.int32)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    return dict(lit=t(buf), off=t(offs), sz=t(sizes), sb=t(seg_begin), segs=t(segs.view(np.uint8)), longest=int(sizes.max()), n=len(streams),
-                offs=offs, sizes=sizes)
-
-
-def _codec(da, fam, g, longest):
-    codec = da.LiteralCodec(g, max(longest, 16))
-    codec.set_block_types(fam.n_btypes)
-    return codec
-
-
-def _split(tin, outs):
-    out = outs["out"].cpu().numpy(); offs = outs["offsets"].cpu().numpy(); sz = outs["sizes"].cpu().numpy()
-    return [out[int(offs[i]):int(offs[i]) + int(sz[i])] for i in range(tin["n"])]
-
-
-def _encode(codec, tin, outs=None):
-    """-> (status, [coded bytes of stream i], the pass that ran)"""
-    outs = outs or codec.alloc_encode_outputs(tin["n"])
-    codec.encode_segments_batch(tin["lit"], tin["off"], tin["sz"], tin["n"], tin["longest"], tin["sb"], tin["segs"], outs)
-    st = codec.status()
-    return st, _split(tin, outs), codec.last_encode_path()
-
-
-def _assert_same(got, ref, streams, what, skip=()):
-    for i, (g, r) in enumerate(zip(got, ref)):
-        if i in skip:
-            continue
-        assert g.size == r.size and (g == r).all(), f"{what}: stream {i} ({streams[i][0]}, {streams[i][1].size} bytes, {streams[i][2].size} segments) differs from the oracle"
 
 
 @pytest.mark.parametrize("key", KEYS)
@@ -81,21 +41,21 @@ def test_bucketed_pass_codes_segment_lists_bit_exact(key, sources):
     import torch
     import divans_amd as da
     fam, g, o, streams, coded = _case(key, sources)
-    tin = _tensors(torch, streams)
+    tin = gh.ragged_tensors(torch, streams)
     assert tin["longest"] == 65536
-    codec = _codec(da, fam, g, tin["longest"])
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     assert codec.last_encode_path() == 0
     codec.set_encode_path(2)
     for what, sub in (("one launch sequence", None), ("launch sequences of 24 streams", 24)):
         if sub:
             codec.set_bucket_batch(sub)
-        st, got, path = _encode(codec, tin)
+        st, got, path = gh.encode_segments(codec, tin)
         assert st == 0 and path == bc.BUCKETED_PATH[key], (what, st, path)
-        _assert_same(got, coded, streams, what)
+        gh.assert_same(got, coded, streams, what)
     codec.set_encode_path(1)
-    st, got, path = _encode(codec, tin)
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, coded, streams, "streaming kernels")
+    gh.assert_same(got, coded, streams, "streaming kernels")
     codec.close()
 
 
@@ -106,22 +66,20 @@ def test_the_default_path_did_not_move(key, sources):
     import divans_amd as da
     fam, g, o, streams, coded = _case(key, sources)
     few = streams[:16]
-    tin = _tensors(torch, few)
-    codec = _codec(da, fam, g, tin["longest"])
-    st, got, path = _encode(codec, tin)
+    tin = gh.ragged_tensors(torch, few)
+    codec = gh.codec_for(da, fam, g, tin["longest"])
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, coded, few, "automatic, with a list")
+    gh.assert_same(got, coded, few, "automatic, with a list")
     outs = codec.alloc_encode_outputs(tin["n"])
     codec.encode_batch(tin["lit"], tin["n"], tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
     assert codec.status() == 0 and codec.last_encode_path() == bc.BUCKETED_PATH[key]
     plain = [po.lit_encode(o, lit) if lit.size else np.zeros(0, np.uint8) for _, lit, _ in few]
-    for i, (a, b) in enumerate(zip(_split(tin, outs), plain)):
-        assert a.size == b.size and (a == b).all(), f"plain entry point: stream {i} ({few[i][0]})"
+    gh.assert_same(gh.split_outputs(outs, tin["n"]), plain, few, "plain entry point")
     codec.set_encode_path(2)      # ... and it stays so once the bucketed pass also serves the lists
     codec.encode_batch(tin["lit"], tin["n"], tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
     assert codec.status() == 0 and codec.last_encode_path() == bc.BUCKETED_PATH[key]
-    for i, (a, b) in enumerate(zip(_split(tin, outs), plain)):
-        assert a.size == b.size and (a == b).all(), f"plain entry point under path 2: stream {i} ({few[i][0]})"
+    gh.assert_same(gh.split_outputs(outs, tin["n"]), plain, few, "plain entry point under path 2")
     codec.close()
 
 
@@ -140,35 +98,17 @@ def test_faulty_lists_are_reported_by_the_bucketed_pass(key, sources):
     assert good[5][0] == "X_edges" and int(good[5][2]["len"][:13].sum()) == 16384
     batches.append(("block type outside the tables, in the stream's third piece", bc.bad_btype(good, 5, outside, 13), (5,)))
     batches.append(("empty stream, list of 5 bytes", bc.empty_stream_with_bytes_in_its_list(good, 4), (4,)))
-    tins = [_tensors(torch, batch) for _, batch, _ in batches]
-    codec = _codec(da, fam, g, max(t["longest"] for t in tins))
+    tins = [gh.ragged_tensors(torch, batch) for _, batch, _ in batches]
+    codec = gh.codec_for(da, fam, g, max(t["longest"] for t in tins))
     codec.set_encode_path(2)
     for (what, batch, skip), tin in zip(batches, tins):
-        st, got, path = _encode(codec, tin)
-        assert st & BAD_SEGMENT and path == bc.BUCKETED_PATH[key], (what, st, path)
-        _assert_same(got, coded, batch, what, skip=skip)
-    st, got, path = _encode(codec, _tensors(torch, good))
+        st, got, path = gh.encode_segments(codec, tin)
+        assert st & gh.BAD_SEGMENT and path == bc.BUCKETED_PATH[key], (what, st, path)
+        gh.assert_same(got, coded, batch, what, skip=skip)
+    st, got, path = gh.encode_segments(codec, gh.ragged_tensors(torch, good))
     assert st == 0 and path == bc.BUCKETED_PATH[key], (st, path)
-    _assert_same(got, coded, good, "the same streams with their lists in order")
+    gh.assert_same(got, coded, good, "the same streams with their lists in order")
     codec.close()
-
-
-def _ir_streams(ir, count):
-    """`count` streams cut from the IR's command list as test_gpu_general_streams.test_many_general_streams_in_one_batch cuts them:
-    stream k = the literals of commands [a, b), with the Copy / Dict boundaries and block types of the file"""
-    lit, segs = ir.literal_segments()
-    ends = np.cumsum(segs["len"].astype(np.int64))
-    span = min(390, max(2, segs.size // 2))
-    streams = []
-    for k in range(count):
-        a = (k * 149) % (segs.size - span); b = a + 1 + (k * 37) % span
-        lo = int(ends[a - 1]) if a else 0
-        hi = int(ends[b - 1])
-        while hi - lo > 65536:      # (a file of few, long Literal commands)
-            b -= 1; hi = int(ends[b - 1])
-        if b > a:
-            streams.append((f"{a}:{b}", lit[lo:hi].copy(), segs[a:b].copy()))
-    return streams
 
 
 @pytest.mark.parametrize("name", ["alice29", "alice29-priors", "random_then_unicode"])
@@ -176,7 +116,7 @@ def test_real_command_lists(name):
     import torch
     import divans_amd as da
     ir = da.CommandIR(irtext.load_ir_text(name))
-    streams = _ir_streams(ir, 32)
+    streams = gh.ir_streams(ir, 32)
     assert len(streams) >= 8 and all(0 < s[1].size <= 65536 for s in streams) and any(s[2].size > 1 for s in streams)
     cfg = ir.lit_config(dynamic_context_mixing=0)
     # made eligible for the bucketed pass here: constant context, mixing value 4 everywhere, one model
@@ -184,20 +124,15 @@ def test_real_command_lists(name):
     ctypes.memset(cfg.mixing_mask, 4, 8192)
     cfg.context_mixing = 0
     ocfg = po.LitConfig.from_buffer_copy(bytes(cfg))
-    coded = _oracle(ocfg, streams)
-    tin = _tensors(torch, streams)
+    coded = gh.oracle_bytes(ocfg, streams)
+    tin = gh.ragged_tensors(torch, streams)
     codec = da.LiteralCodec(cfg, max(tin["longest"], 16))
     codec.set_block_types(ir.num_block_types)
     codec.set_encode_path(2)
     outs = codec.alloc_encode_outputs(tin["n"])
-    st, got, path = _encode(codec, tin, outs)
+    st, got, path = gh.encode_segments(codec, tin, outs)
     assert st == 0 and path == 2, (st, path)
-    _assert_same(got, coded, streams, name)
-    back = torch.zeros_like(tin["lit"])
-    codec.decode_segments_batch(outs["out"], outs["offsets"], outs["sizes"], tin["n"], tin["longest"], tin["sb"], tin["segs"], back, tin["off"], tin["sz"])
-    assert codec.status() == 0
-    back = back.cpu().numpy()
-    for (nm, lit, _), off in zip(streams, tin["offs"]):
-        assert (back[int(off):int(off) + lit.size] == lit).all(), (name, nm)
+    gh.assert_same(got, coded, streams, name)
+    gh.assert_round_trip_segments(torch, codec, tin, outs, streams, name)
     codec.close()
     ir.close()

@@ -36,6 +36,7 @@ import numpy as np
 import pytest
 
 import caller_stream_cases as cs
+import gpu_harness as gh
 import pyoracle as po
 import segment_cases as sc
 
@@ -163,12 +164,6 @@ def _split(side, outs, n):
     return [out[int(offs[i]):int(offs[i]) + int(sz[i])] for i in range(n)]
 
 
-def _same(got, ref, what):
-    assert len(got) == len(ref)
-    for i, (a, b) in enumerate(zip(got, ref)):
-        assert a.size == b.size and (a == b).all(), f"{what}: stream {i} differs from the oracle ({a.size} bytes against {b.size})"
-
-
 def _codec(da, side, fam, g, longest=cs.SMALL_LONGEST):
     with side.torch.cuda.stream(side.stream):
         codec = da.LiteralCodec(g, longest, stream=side.stream)
@@ -260,7 +255,7 @@ def test_a_read_that_does_not_wait_sees_the_previous_contents(sources, side):
         if not ev.query():      # else the host stalled past the delay and the early read shows nothing
             shown += 1
             assert (early_sizes == -1).all() and (early_offsets == -1).all(), (r, early_sizes[:8])
-        _same(_split(side, outs, n), rd["plain"], f"round {r}: encode_batch")
+        gh.assert_same(_split(side, outs, n), rd["plain"], None, f"round {r}: encode_batch")
     assert shown >= 2, f"the delay had run out before the early read in {len(rounds) + 1 - shown} of {len(rounds) + 1} rounds"
     assert codec.status() == 0
     codec.close()
@@ -300,14 +295,14 @@ def test_device_entry_points_delayed(key, sources, side):
                 ev = side.delay()
                 codec.encode_batch(tin["lit"], n, tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
                 held.append(not ev.query())
-                _same(_split(side, outs, n), plain, what + ": encode_batch")
+                gh.assert_same(_split(side, outs, n), plain, None, what + ": encode_batch")
                 assert codec.last_encode_path() in ((1,) if path == 1 else (2, 3)), what
                 _blank(side, outs)
                 with torch.cuda.stream(side.stream):
                     chunks.zero_()
                 side.delay()
                 codec.encode_batch(tin["lit"], n, tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"], chunk_bytes=chunks)
-                _same(_split(side, outs, n), plain, what + ": encode_batch_chunks")
+                gh.assert_same(_split(side, outs, n), plain, None, what + ": encode_batch_chunks")
                 assert side.host(chunks)[:, 0].tolist() == [c.size for c in plain], what
                 # encode_packed in three sub-batches through codec-owned slots; pack_streams against a numpy prefix sum
                 want_off, want_total = cs.packed_layout(plain)
@@ -317,7 +312,7 @@ def test_device_entry_points_delayed(key, sources, side):
                 codec.encode_packed(tin["lit"], n, tin["longest"], packed, poff, psz, total, in_offsets=tin["off"], in_sizes=tin["sz"], sub_batch=16)
                 hp, ho, hs, ht = side.host(packed), side.host(poff), side.host(psz), side.host(total)
                 assert int(ht[0]) == want_total and (ho == want_off).all() and hs.tolist() == [c.size for c in plain], what + ": encode_packed"
-                _same([hp[int(a):int(a) + int(b)] for a, b in zip(ho, hs)], plain, what + ": encode_packed")
+                gh.assert_same([hp[int(a):int(a) + int(b)] for a, b in zip(ho, hs)], plain, None, what + ": encode_packed")
                 with torch.cuda.stream(side.stream):
                     packed.fill_(SENTINEL); poff.fill_(-1); total.fill_(-1)
                 _blank(side, outs)
@@ -327,7 +322,7 @@ def test_device_entry_points_delayed(key, sources, side):
                 held.append(not ev.query())
                 hp, ho, ht = side.host(packed), side.host(poff), side.host(total)
                 assert int(ht[0]) == want_total and (ho == want_off).all(), what + ": pack_streams"
-                _same([hp[int(a):int(a) + c.size] for a, c in zip(ho, plain)], plain, what + ": pack_streams")
+                gh.assert_same([hp[int(a):int(a) + c.size] for a, c in zip(ho, plain)], plain, None, what + ": pack_streams")
                 if True:      # (every family with list-free calls: the pairs under the configuration's own block type)
                     side.delay()
                     with torch.cuda.stream(side.stream):
@@ -341,7 +336,7 @@ def test_device_entry_points_delayed(key, sources, side):
             ev = side.delay()
             codec.encode_segments_batch(tin["lit"], tin["off"], tin["sz"], n, tin["longest"], tin["sb"], tin["segs"], outs)
             held.append(not ev.query())
-            _same(_split(side, outs, n), listed, what + ": encode_segments_batch")
+            gh.assert_same(_split(side, outs, n), listed, None, what + ": encode_segments_batch")
         # the decoders read the ORACLE's bytes: a wrong encoder above cannot hide a wrong decoder
         for coded, name in ((plain, "decode_batch"), (listed, "decode_segments_batch")):
             if coded is None:
@@ -415,7 +410,7 @@ def test_command_entry_points_delayed(sources, side):
             _blank(side, outs)
             side.delay()
             codec.encode_commands_batch(d_raw, t["raw_off"], t["raw_sz"], n, t["cmd_begin"], t["cmds"], lay["lit_longest"], outs, lit_sz, *ins, **hist)
-            _same(_split(side, outs, n), coded, f"{what}, path {path}: encode_commands_batch")
+            gh.assert_same(_split(side, outs, n), coded, None, f"{what}, path {path}: encode_commands_batch")
             assert side.host(lit_sz).tolist() == [s["lit"].size for s in streams], (what, path)
             assert codec.status() == 0 and codec.last_encode_path() in ((1,) if path == 1 else (2, 3)), (what, path)
     codec.close()
@@ -559,7 +554,7 @@ def test_setters_behind_a_delayed_launch(key, sources, side):
         cs.assert_no_generic_instance(codec.last_decode_kernel())
 
         def check():
-            _same(_split(side, out, n), rounds[r]["listed"], f"{key}: encode_segments_batch {what}")
+            gh.assert_same(_split(side, out, n), rounds[r]["listed"], None, f"{key}: encode_segments_batch {what}")
             _decoded(side, back, tin, f"{key}: decode_segments_batch {what}")
         return check
 
@@ -635,7 +630,7 @@ def test_placement_search_call_by_call_delayed(sources, side):
         side.delay()
         codec.encode_batch(d_in[r], n, L, outs[r])
         got = _split(side, outs[r], n)
-        _same(got[:48], [po.lit_encode(o, b) for b in both[r][:48]], f"round {r}: encode_batch")
+        gh.assert_same(got[:48], [po.lit_encode(o, b) for b in both[r][:48]], None, f"round {r}: encode_batch")
     codec.search_tables(4)
     pl = codec.table_placement()
     assert pl["policy_candidates"] == 4 and pl["tried"] == 0 and not pl["searching"]
@@ -704,13 +699,13 @@ def test_host_wrappers_delayed(key, sources, side):
             pipelined copy that does not wait for its slice's kernel delivers well-formed bytes of the wrong round"""
             ob, oc = both[1 - r]
             p2, o2, s2 = codec.encode_host(ob, L)
-            _same([p2[int(a):int(a) + int(z)] for a, z in zip(o2, s2)], oc, f"{what}: encode_host of the other round")
+            gh.assert_same([p2[int(a):int(a) + int(z)] for a, z in zip(o2, s2)], oc, None, f"{what}: encode_host of the other round")
             assert (codec.decode_host(p2, o2, s2, L) == ob).all(), what
 
         def check(res, name):
             packed, offs, sizes = res
             assert packed.size == want_total and (offs == want_off).all() and sizes.tolist() == [c.size for c in coded], f"{what}: {name}: total, offsets or sizes are not this call's"
-            _same([packed[int(a):int(a) + int(b)] for a, b in zip(offs, sizes)], coded, f"{what}: {name}")
+            gh.assert_same([packed[int(a):int(a) + int(b)] for a, b in zip(offs, sizes)], coded, None, f"{what}: {name}")
             return res
 
         side.delay()
@@ -764,7 +759,7 @@ def test_long_streams_and_piecewise_coding_delayed(key, sources, side):
         _blank(side, outs)
         side.delay()
         codec.encode_batch(tin["lit"], 2, tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
-        _same(_split(side, outs, 2), coded, f"{key}, round {r}: encode_batch at the chunk seam")
+        gh.assert_same(_split(side, outs, 2), coded, None, f"{key}, round {r}: encode_batch at the chunk seam")
         cbuf, coffs, csz = _coded_layout(coded)
         back = side.full(tin["buf"].size, SENTINEL, torch.uint8)
         d_c, d_co, d_cs = side.up(cbuf), side.up(coffs), side.up(csz)
@@ -832,7 +827,7 @@ def test_four_codecs_on_four_threads(lineup, sources):
                     want_off, want_total = cs.packed_layout(plain)
                     hp, ho, ht = s.host(packed), s.host(poff), s.host(total)
                     assert int(ht[0]) == want_total and (ho == want_off).all(), what
-                    _same([hp[int(a):int(a) + c.size] for a, c in zip(ho, plain)], plain, what + ": encode_batch + pack_streams")
+                    gh.assert_same([hp[int(a):int(a) + c.size] for a, c in zip(ho, plain)], plain, None, what + ": encode_batch + pack_streams")
                     codec.decode_batch(packed, poff, outs["sizes"], n, tin["longest"], back, out_offsets=tin["off"], out_sizes=tin["sz"])
                     cs.assert_no_generic_instance(codec.last_decode_kernel())
                     _decoded(s, back, tin, what + ": decode_batch")
@@ -840,7 +835,7 @@ def test_four_codecs_on_four_threads(lineup, sources):
                         back.fill_(SENTINEL)
                 _blank(s, outs)
                 codec.encode_segments_batch(tin["lit"], tin["off"], tin["sz"], n, tin["longest"], tin["sb"], tin["segs"], outs)
-                _same(_split(s, outs, n), listed, what + ": encode_segments_batch")
+                gh.assert_same(_split(s, outs, n), listed, None, what + ": encode_segments_batch")
                 codec.decode_segments_batch(outs["out"], outs["offsets"], outs["sizes"], n, tin["longest"], tin["sb"], tin["segs"], back, tin["off"], tin["sz"])
                 cs.assert_no_generic_instance(codec.last_decode_kernel())
                 _decoded(s, back, tin, what + ": decode_segments_batch")

@@ -20,9 +20,10 @@ import numpy as np
 import pytest
 
 import cdf_ops_sweeps as sw
-from test_gpu_reference_unit_tests import IMPLS
+import gpu_harness as gh
 
 pytestmark = pytest.mark.gpu
+IMPLS = gh.implementations()
 
 
 @pytest.fixture(scope="module")

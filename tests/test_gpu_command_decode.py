@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import command_cases as cc
+import gpu_harness as gh
 import irtext
 import pyoracle as po
 import segment_cases as sc
@@ -23,69 +24,15 @@ def sources(corpus, random_then_unicode, shuffle384):
     return (corpus, random_then_unicode, shuffle384)
 
 
-def _code(ocfg, streams):
-    return [po.lit_segments_encode(ocfg, s["lit"], s["segs"]["len"], s["segs"]["btype"], s["segs"]["last8"]) for s in streams]
-
-
 def _case(fam, sources):
     """the family's configurations, its directed batch, the oracle's bytes and the batch's layout: computed once, shared, never written to"""
     if fam.name not in _CASES:
         import divans_amd as da
         g, o = fam.pair(da, po)
         streams = cc.directed(fam, sources)
-        coded = _code(o, streams)
+        coded = gh.oracle_bytes(o, streams)
         _CASES[fam.name] = (g, o, streams, coded, cc.layout(streams, coded))
     return _CASES[fam.name]
-
-
-def _tensors(torch, lay):
-    dev = torch.device("cuda")
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in lay.items() if isinstance(v, np.ndarray)}
-
-
-def _decode(torch, codec, lay, t, with_ins=True):
-    """-> (status, the whole raw buffer, stream flags, name of the kernel that ran)"""
-    raw = t["raw"].clone()
-    flags = torch.zeros(lay["n"] + 16, dtype=torch.uint8, device=raw.device)
-    codec.set_stream_flags(flags)
-    ins = (t["ins"], t["ins_off"], t["ins_sz"]) if with_ins else (None, None, None)
-    codec.decode_commands_batch(t["coded"], t["coded_off"], t["coded_sz"], lay["n"], t["cmd_begin"], t["cmds"], t["lit_sz"], lay["lit_longest"],
-                                raw, t["raw_off"], t["raw_sz"], *ins)
-    st = codec.status()
-    codec.set_stream_flags(None)
-    return st, raw.cpu().numpy(), flags.cpu().numpy(), codec.last_decode_kernel()
-
-
-def _b(v):
-    return "true" if v else "false"
-
-
-def _assert_kernel(fam, name, what):
-    """lit_decode2_cmd_kernel<MM, CTXC, MIX, caches>: the high-row caches in the 2-way organisation (1 | 16, with mixing 1 | 2 | 16), or none"""
-    mm = fam.mm if fam.mm >= 0 else -1
-    caches = (19 if fam.mix else 17) if fam.cached else 0
-    assert name == f"divans_hip::lit_decode2_cmd_kernel<{mm}, {_b(fam.ctxc)}, {_b(fam.mix)}, {caches}>", (what, name)
-
-
-def _assert_raw(got, lay, streams, what, skip=()):
-    """the whole raw buffer against the expectation, sentinels included (the raw ranges of the streams in `skip` left out)"""
-    same = got == lay["expect"]
-    for i in skip:
-        ro = int(lay["raw_off"][i]); same[ro:ro + int(lay["raw_sz"][i])] = True
-    if same.all():
-        return
-    at = int(np.argmin(same))
-    inside = [i for i in range(lay["n"]) if int(lay["raw_off"][i]) <= at < int(lay["raw_off"][i]) + int(lay["raw_sz"][i])]
-    if inside:
-        i = inside[0]
-        raise AssertionError(f"{what}: stream {i} ({streams[i]['name']}, {int(lay['raw_sz'][i])} raw bytes) wrong from its byte {at - int(lay['raw_off'][i])}")
-    raise AssertionError(f"{what}: sentinel byte {at} of the raw buffer overwritten with {int(got[at])}")
-
-
-def _codec(da, fam, g, longest):
-    codec = da.LiteralCodec(g, max(longest, 16))
-    codec.set_block_types(fam.n_btypes)
-    return codec
 
 
 @pytest.mark.parametrize("fam", sc.FAMILIES, ids=repr)
@@ -95,18 +42,18 @@ def test_directed_batch(fam, sources):
     import torch
     import divans_amd as da
     g, o, streams, coded, lay = _case(fam, sources)
-    t = _tensors(torch, lay)
-    codec = _codec(da, fam, g, lay["lit_longest"])
+    t = gh.to_device(torch, lay)
+    codec = gh.codec_for(da, fam, g, lay["lit_longest"])
     steps = [("2 workgroups", lambda c: c.set_geometry(blocks=2)), ("1 workgroup", lambda c: c.set_geometry(blocks=1)),
              ("direct-mapped decoder asked for", lambda c: c.set_decoder(2))]
     if fam.cached:
         steps.append(("tiny 2-way caches with low-row caches asked for", lambda c: c.set_decoder(3, (8, 8, 8, 8), (5, 5, 5, 5), blocks=2)))
     for what, setup in steps:
         setup(codec)
-        st, raw, flags, name = _decode(torch, codec, lay, t)
+        st, raw, flags, name = gh.decode_commands(torch, codec, lay, t)
         assert st == 0, (what, st, name)
-        _assert_kernel(fam, name, what)
-        _assert_raw(raw, lay, streams, what)
+        gh.assert_command_kernel(fam, name, what)
+        gh.assert_raw(raw, lay, streams, what)
         assert not flags.any(), what
     codec.close()
 
@@ -117,29 +64,15 @@ def test_segment_path_still_decodes_the_same_batch(fam, sources):
     import torch
     import divans_amd as da
     g, o, streams, coded, lay = _case(fam, sources)
-    dev = torch.device("cuda")
-    t = _tensors(torch, lay)
-    sizes = np.array([s["lit"].size for s in streams], dtype=np.int32)
-    offs = np.concatenate([[0], np.cumsum(sizes[:-1].astype(np.int64))]).astype(np.int64)
-    segs = np.concatenate([s["segs"] for s in streams] + [np.zeros(1, sc.SEG_DTYPE)])
-    seg_begin = np.concatenate([[0], np.cumsum([s["segs"].size for s in streams])]).astype(np.int32)
-    lit = np.concatenate([s["lit"] for s in streams] + [np.zeros(64, np.uint8)])
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    back = torch.zeros(lit.size, dtype=torch.uint8, device=dev)
-    codec = _codec(da, fam, g, lay["lit_longest"])
+    t = gh.to_device(torch, lay)
+    tin = gh.input_tensors(torch, gh.as_tuples(streams))
+    codec = gh.codec_for(da, fam, g, lay["lit_longest"])
     codec.set_geometry(blocks=2)
-    codec.decode_segments_batch(t["coded"], t["coded_off"], t["coded_sz"], len(streams), lay["lit_longest"], d(seg_begin), d(segs.view(np.uint8)), back, d(offs), d(sizes))
-    st = codec.status(); name = codec.last_decode_kernel()
+    st, back, name = gh.decode_segments(torch, codec, dict(tin, longest=lay["lit_longest"]), (t["coded"], t["coded_off"], t["coded_sz"]))
     codec.close()
     mm = fam.mm if fam.mm >= 0 else -1
-    assert st == 0 and "lit_decode2_kernel_" in name and f"<{mm}, {_b(fam.ctxc)}, {_b(fam.mix)}, true, " in name, (st, name)
-    assert (back.cpu().numpy() == lit).all()
-
-
-def _ir_stream(ir, name):
-    cmds, ins = ir.device_commands()
-    lit, segs = ir.literal_segments()
-    return dict(name=name, cmds=cmds, lit=lit, ins=ins, raw=ir.expand(), segs=segs)
+    assert st == 0 and "lit_decode2_kernel_" in name and f"<{mm}, {gh.tf(fam.ctxc)}, {gh.tf(fam.mix)}, true, " in name, (st, name)
+    assert (back == tin["lit"].cpu().numpy()).all()
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -150,14 +83,14 @@ def test_golden_ir_decodes_to_its_expansion(name, mixing):
     ir = da.CommandIR(irtext.load_ir_text(name))
     cfg = ir.lit_config(dynamic_context_mixing=mixing, use_context_map=1)
     ocfg = po.LitConfig.from_buffer_copy(bytes(cfg))
-    s = _ir_stream(ir, name)
-    lay = cc.layout([s], _code(ocfg, [s]))
+    s = gh.ir_stream(ir, name)
+    lay = cc.layout([s], gh.oracle_bytes(ocfg, [s]))
     codec = da.LiteralCodec(cfg, lay["lit_longest"])
     codec.set_block_types(ir.num_block_types)
-    st, raw, flags, kname = _decode(torch, codec, lay, _tensors(torch, lay), with_ins=s["ins"].size > 0)
+    st, raw, flags, kname = gh.decode_commands(torch, codec, lay, gh.to_device(torch, lay), with_ins=s["ins"].size > 0)
     codec.close(); ir.close()
     assert st == 0 and "lit_decode2_cmd_kernel" in kname, (st, kname)
-    _assert_raw(raw, lay, [s], name)
+    gh.assert_raw(raw, lay, [s], name)
     assert not flags.any()
 
 
@@ -173,14 +106,14 @@ def test_ragged_batch_of_command_list_prefixes():
     streams = cc.prefix_streams(cmds, lit, ins, 40)
     full = ir.expand()
     assert all((s["raw"] == full[:s["raw"].size]).all() for s in streams) and len(set(s["raw"].size for s in streams)) > 30
-    lay = cc.layout(streams, _code(ocfg, streams))
+    lay = cc.layout(streams, gh.oracle_bytes(ocfg, streams))
     codec = da.LiteralCodec(cfg, lay["lit_longest"])
     codec.set_block_types(ir.num_block_types)
     codec.set_geometry(blocks=1)
-    st, raw, flags, kname = _decode(torch, codec, lay, _tensors(torch, lay))
+    st, raw, flags, kname = gh.decode_commands(torch, codec, lay, gh.to_device(torch, lay))
     codec.close(); ir.close()
     assert st == 0, (st, kname)
-    _assert_raw(raw, lay, streams, "prefixes")
+    gh.assert_raw(raw, lay, streams, "prefixes")
     assert not flags.any()
 
 
@@ -197,22 +130,22 @@ def test_faulty_lists_are_reported_and_contained(fam, sources):
     victim, neighbour = cc.victim_base(fam, sources)
     at = 3
     good = [neighbour, neighbour, neighbour, victim, neighbour, neighbour, neighbour]
-    coded = _code(o, good)
-    codec = _codec(da, fam, g, 64)
+    coded = gh.oracle_bytes(o, good)
+    codec = gh.codec_for(da, fam, g, 64)
     codec.set_geometry(blocks=1)
     lay = cc.layout(good, coded)
-    st, raw, flags, name = _decode(torch, codec, lay, _tensors(torch, lay))
+    st, raw, flags, name = gh.decode_commands(torch, codec, lay, gh.to_device(torch, lay))
     assert st == 0 and not flags.any(), (st, name)
-    _assert_raw(raw, lay, good, "the good list")
+    gh.assert_raw(raw, lay, good, "the good list")
     for what, cmds, nlit, bit in cc.faulty_lists(fam, victim):
         batch = list(good)
         batch[at] = dict(victim, cmds=cmds)
         lay = cc.layout(batch, coded, lit_sizes=[nlit if i == at else s["lit"].size for i, s in enumerate(batch)])
-        st, raw, flags, name = _decode(torch, codec, lay, _tensors(torch, lay))
+        st, raw, flags, name = gh.decode_commands(torch, codec, lay, gh.to_device(torch, lay))
         other = cc.BAD_SEGMENT if bit == cc.BAD_COMMAND else cc.BAD_COMMAND
         assert st & bit and not st & other and not st & ~(bit | cc.BAD_STREAM), (what, st, name)
         assert flags[at] == 1 and int(flags.sum()) == 1, (what, flags[:lay["n"]].tolist())
-        _assert_raw(raw, lay, batch, what, skip=(at,))
+        gh.assert_raw(raw, lay, batch, what, skip=(at,))
     codec.close()
 
 
@@ -226,13 +159,13 @@ def test_insert_command_without_insert_bytes_is_a_bad_command(sources):
     rng = np.random.default_rng(5)
     plain = cc.Stream("no_inserts", fam, sc._Data(sources, rng), rng).lit(20).copy(9, 4).lit(7).done()
     batch = [plain, victim, plain]
-    lay = cc.layout(batch, _code(o, batch))
-    codec = _codec(da, fam, g, 64)
-    st, raw, flags, name = _decode(torch, codec, lay, _tensors(torch, lay), with_ins=False)
+    lay = cc.layout(batch, gh.oracle_bytes(o, batch))
+    codec = gh.codec_for(da, fam, g, 64)
+    st, raw, flags, name = gh.decode_commands(torch, codec, lay, gh.to_device(torch, lay), with_ins=False)
     codec.close()
     assert st & cc.BAD_COMMAND and not st & cc.BAD_SEGMENT, (st, name)
     assert flags[:3].tolist() == [0, 1, 0]
-    _assert_raw(raw, lay, batch, "no insert bytes", skip=(1,))
+    gh.assert_raw(raw, lay, batch, "no insert bytes", skip=(1,))
 
 
 def test_wrap_checked_speed_is_refused(sources):
@@ -247,7 +180,7 @@ def test_wrap_checked_speed_is_refused(sources):
         g.literal_adaptation[i].inc, g.literal_adaptation[i].lim = speed
     victim, neighbour = cc.victim_base(fam, sources)
     lay = cc.layout([neighbour], [np.zeros(16, np.uint8)])
-    codec = _codec(da, fam, g, 64)
+    codec = gh.codec_for(da, fam, g, 64)
     with pytest.raises(da.DivansGpuError, match="command lists need decoder generation 2 or 3"):
-        _decode(torch, codec, lay, _tensors(torch, lay))
+        gh.decode_commands(torch, codec, lay, gh.to_device(torch, lay))
     codec.close()

@@ -11,23 +11,19 @@ import pytest
 
 import command_cases as cc
 import command_encode_cases as ce
+import gpu_harness as gh
 import irtext
 import pyoracle as po
 import segment_cases as sc
 
 pytestmark = pytest.mark.gpu
 NAMES = ["alice29", "alice29-q11", "alice29-priors", "asyoulik", "random_then_unicode", "ends_with_truncated_dictionary"]
-OUT_SENTINEL, SIZE_SENTINEL = 0x3C, 0x5A5A5A5A
 _CASES = {}
 
 
 @pytest.fixture(scope="module")
 def sources(corpus, random_then_unicode, shuffle384):
     return (corpus, random_then_unicode, shuffle384)
-
-
-def _code(ocfg, streams):
-    return [po.lit_segments_encode(ocfg, s["lit"], s["segs"]["len"], s["segs"]["btype"], s["segs"]["last8"]) for s in streams]
 
 
 def _lay(streams):
@@ -44,88 +40,18 @@ def _case(fam, sources):
         g, o = fam.pair(da, po)
         batches = {}
         for what, streams in (("directed", cc.directed(fam, sources)), ("count_edges", ce.count_edges(fam, sources))):
-            batches[what] = (streams, _code(o, streams), _lay(streams))
+            batches[what] = (streams, gh.oracle_bytes(o, streams), _lay(streams))
         _CASES[fam.name] = (g, o, batches)
     return _CASES[fam.name]
 
 
-def _tensors(torch, lay):
-    dev = torch.device("cuda")
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in lay.items() if isinstance(v, np.ndarray)}
-
-
-def _codec(da, fam, g, longest):
-    codec = da.LiteralCodec(g, max(longest, 16))
-    codec.set_block_types(fam.n_btypes)
-    return codec
-
-
-def _outputs(torch, codec, n):
-    outs = codec.alloc_encode_outputs(n)        # slots of divans_gpu_lit_encode_bound(the codec's max_stream_len)
-    outs["out"].fill_(OUT_SENTINEL); outs["offsets"].fill_(-1); outs["sizes"].fill_(-1)
-    return outs
-
-
-def _encode(torch, codec, lay, t, n=None, with_ins=True, lit_cap=None, outs=None):
-    """-> dict(status, coded = [bytes of stream i], lit_sz, flags, out = the whole slot buffer, spans = [(begin, end) of stream i in it])
-    and asserts that the call left its inputs and everything behind its outputs alone"""
-    n = lay["n"] if n is None else n
-    cap = lay["lit_longest"] if lit_cap is None else lit_cap
-    outs = outs or _outputs(torch, codec, n)
-    lit_sz = torch.full((n + 16,), SIZE_SENTINEL, dtype=torch.int32, device=t["raw"].device)
-    flags = torch.zeros(n + 16, dtype=torch.uint8, device=t["raw"].device)
-    codec.set_stream_flags(flags)
-    ins = (t["ins"], t["ins_off"], t["ins_sz"]) if with_ins else (None, None, None)
-    try:
-        codec.encode_commands_batch(t["raw"], t["raw_off"], t["raw_sz"], n, t["cmd_begin"], t["cmds"], cap, outs, lit_sz, *ins)
-        st = codec.status()
-    finally:
-        codec.set_stream_flags(None)
-    out = outs["out"].cpu().numpy(); offs = outs["offsets"].cpu().numpy(); sz = outs["sizes"].cpu().numpy()
-    for k in ("raw", "cmds", "cmd_begin", "ins", "raw_off", "raw_sz", "ins_off", "ins_sz"):
-        assert (t[k].cpu().numpy() == np.ascontiguousarray(lay[k])).all(), f"the call wrote to its input `{k}`"
-    lit_sz = lit_sz.cpu().numpy(); flags = flags.cpu().numpy()
-    assert (lit_sz[n:] == SIZE_SENTINEL).all() and not flags[n:].any() and (out[n * outs["slot"]:] == OUT_SENTINEL).all(), "bytes written behind the outputs"
-    spans = [(int(offs[i]), int(offs[i]) + int(sz[i])) for i in range(n)]
-    for i, (b, e) in enumerate(spans):
-        assert i * outs["slot"] <= b <= e <= (i + 1) * outs["slot"], f"stream {i} lies outside its slot: {b}..{e}"
-    return dict(status=st, coded=[out[b:e] for b, e in spans], lit_sz=lit_sz[:n], flags=flags[:n], out=out, spans=spans, slot=outs["slot"])
-
-
 def _segments_call(torch, codec, streams, cap):
     """divans_gpu_lit_encode_segments_batch on the executor's lists for the same streams, into slots pre-filled the same way"""
-    dev = torch.device("cuda")
-    n = len(streams)
-    sizes = np.array([s["lit"].size for s in streams], dtype=np.int32)
-    offs = np.concatenate([[0], np.cumsum(sizes[:-1].astype(np.int64))]).astype(np.int64)
-    segs = np.concatenate([s["segs"] for s in streams] + [np.zeros(1, sc.SEG_DTYPE)])
-    seg_begin = np.concatenate([[0], np.cumsum([s["segs"].size for s in streams])]).astype(np.int32)
-    lit = np.concatenate([s["lit"] for s in streams] + [np.zeros(64, np.uint8)])
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    outs = _outputs(torch, codec, n)
-    codec.encode_segments_batch(d(lit), d(offs), d(sizes), n, cap, d(seg_begin), d(segs.view(np.uint8)), outs)
-    st = codec.status()
-    out = outs["out"].cpu().numpy(); o = outs["offsets"].cpu().numpy(); z = outs["sizes"].cpu().numpy()
-    return st, out, [(int(o[i]), int(o[i]) + int(z[i])) for i in range(n)]
-
-
-def _assert_coded(res, streams, coded, what, skip=()):
-    for i, (got, ref) in enumerate(zip(res["coded"], coded)):
-        if i in skip:
-            continue
-        assert got.size == ref.size and (got == ref).all(), f"{what}: stream {i} ({streams[i]['name']}, {streams[i]['cmds'].size} commands) differs from the oracle"
-        assert int(res["lit_sz"][i]) == streams[i]["lit"].size, (what, i, streams[i]["name"])
-
-
-def _paths(codec, da):
-    """the encode paths to run: the streaming kernels, and the bucketed passes where the codec has them"""
-    paths = [1]
-    try:
-        codec.set_encode_path(2)
-        paths.append(2)
-    except da.DivansGpuError:
-        pass
-    return paths
+    tin = gh.input_tensors(torch, gh.as_tuples(streams))
+    outs = gh.encode_outputs(codec, tin["n"])
+    st, _, _ = gh.encode_segments(codec, dict(tin, longest=cap), outs)
+    o = outs["offsets"].cpu().numpy(); z = outs["sizes"].cpu().numpy()
+    return st, outs["out"].cpu().numpy(), [(int(o[i]), int(o[i]) + int(z[i])) for i in range(tin["n"])]
 
 
 @pytest.mark.parametrize("fam", sc.FAMILIES, ids=repr)
@@ -133,25 +59,25 @@ def test_directed_batches(fam, sources):
     import torch
     import divans_amd as da
     g, o, batches = _case(fam, sources)
-    codec = _codec(da, fam, g, max(lay["lit_longest"] for _, _, lay in batches.values()))      # one codec: one allocation of the tables
-    paths = _paths(codec, da)
+    codec = gh.codec_for(da, fam, g, max(lay["lit_longest"] for _, _, lay in batches.values()))      # one codec: one allocation of the tables
+    paths = gh.encode_paths(codec, da)
     for which, (streams, coded, lay) in batches.items():
-        t = _tensors(torch, lay)
+        t = gh.to_device(torch, lay)
         for path in paths:
             what = f"{which}, path {path}"
             codec.set_encode_path(path)
-            res = _encode(torch, codec, lay, t)
+            res = gh.encode_commands(torch, codec, lay, t)
             assert res["status"] == 0 and not res["flags"].any(), (what, res["status"], res["flags"].tolist())
             assert codec.last_encode_path() == 1 if path == 1 else codec.last_encode_path() in (2, 3), (what, codec.last_encode_path())
-            _assert_coded(res, streams, coded, what)
+            gh.assert_coded(res, streams, coded, what)
             # what the segment call leaves of the fill outside the coded streams, this call leaves too
             st, seg_out, seg_spans = _segments_call(torch, codec, streams, lay["lit_longest"])
             assert st == 0 and seg_spans == res["spans"], what
             outside = np.ones(seg_out.size, bool)
             for b, e in seg_spans:
                 outside[b:e] = False
-            kept = outside & (seg_out == OUT_SENTINEL)
-            assert (res["out"][kept] == OUT_SENTINEL).all(), f"{what}: slot bytes overwritten that the segment call leaves alone"
+            kept = outside & (seg_out == gh.OUT_SENTINEL)
+            assert (res["out"][kept] == gh.OUT_SENTINEL).all(), f"{what}: slot bytes overwritten that the segment call leaves alone"
     codec.close()
 
 
@@ -163,11 +89,11 @@ def test_one_stream(sources):
     streams, coded, _ = batches["directed"]
     k = next(i for i, s in enumerate(streams) if s["name"] == "lit1to17_each_then_copy")
     lay = _lay([streams[k]])
-    codec = _codec(da, fam, g, lay["lit_longest"])
-    res = _encode(torch, codec, lay, _tensors(torch, lay))
+    codec = gh.codec_for(da, fam, g, lay["lit_longest"])
+    res = gh.encode_commands(torch, codec, lay, gh.to_device(torch, lay))
     codec.close()
     assert res["status"] == 0 and not res["flags"].any()
-    _assert_coded(res, [streams[k]], [coded[k]], "one stream")
+    gh.assert_coded(res, [streams[k]], [coded[k]], "one stream")
 
 
 @pytest.mark.parametrize("fam", sc.FAMILIES, ids=repr)
@@ -176,27 +102,13 @@ def test_round_trip_through_the_command_decoder(fam, sources):
     import torch
     import divans_amd as da
     g, o, batches = _case(fam, sources)
-    codec = _codec(da, fam, g, max(lay["lit_longest"] for _, _, lay in batches.values()))
+    codec = gh.codec_for(da, fam, g, max(lay["lit_longest"] for _, _, lay in batches.values()))
     codec.set_geometry(blocks=2)        # tables of 32 streams, not of a full grid; every group codes and decodes several streams in a row
     for which, (streams, coded, lay) in batches.items():
-        res = _encode(torch, codec, lay, _tensors(torch, lay))
+        res = gh.encode_commands(torch, codec, lay, gh.to_device(torch, lay))
         assert res["status"] == 0, (which, res["status"])
-        back = cc.layout(streams, [c.copy() for c in res["coded"]], lit_sizes=res["lit_sz"].tolist())
-        assert (back["expect"] == lay["expect"]).all()
-        t = _tensors(torch, back)
-        raw = t["raw"].clone()
-        codec.decode_commands_batch(t["coded"], t["coded_off"], t["coded_sz"], back["n"], t["cmd_begin"], t["cmds"], t["lit_sz"], back["lit_longest"],
-                                    raw, t["raw_off"], t["raw_sz"], t["ins"], t["ins_off"], t["ins_sz"])
-        st = codec.status()
-        assert st == 0, (which, st)
-        assert (raw.cpu().numpy() == back["expect"]).all(), f"{which}: the decoder does not give the raw buffer back"
+        gh.round_trip_commands(torch, codec, streams, res, lay, which)
     codec.close()
-
-
-def _ir_stream(ir, name):
-    cmds, ins = ir.device_commands()
-    lit, segs = ir.literal_segments()
-    return dict(name=name, cmds=cmds, lit=lit, ins=ins, raw=ir.expand(), segs=segs)
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -207,17 +119,17 @@ def test_golden_ir_codes_as_its_segments(name, mixing):
     ir = da.CommandIR(irtext.load_ir_text(name))
     cfg = ir.lit_config(dynamic_context_mixing=mixing, use_context_map=1)
     ocfg = po.LitConfig.from_buffer_copy(bytes(cfg))
-    s = _ir_stream(ir, name)
+    s = gh.ir_stream(ir, name)
     lay = _lay([s])
     codec = da.LiteralCodec(cfg, lay["lit_longest"])
     codec.set_block_types(ir.num_block_types)
-    res = _encode(torch, codec, lay, _tensors(torch, lay), with_ins=s["ins"].size > 0)
+    res = gh.encode_commands(torch, codec, lay, gh.to_device(torch, lay), with_ins=s["ins"].size > 0)
     st, seg_out, seg_spans = _segments_call(torch, codec, [s], lay["lit_longest"])
     codec.close(); ir.close()
     assert res["status"] == 0 and st == 0 and not res["flags"].any(), (res["status"], st)
     b, e = seg_spans[0]
     assert res["spans"] == seg_spans and (res["coded"][0] == seg_out[b:e]).all(), "differs from encode_segments_batch on literal_segments()"
-    _assert_coded(res, [s], _code(ocfg, [s]), name)
+    gh.assert_coded(res, [s], gh.oracle_bytes(ocfg, [s]), name)
 
 
 def test_ragged_batch_of_command_list_prefixes():
@@ -233,10 +145,10 @@ def test_ragged_batch_of_command_list_prefixes():
     lay = _lay(streams)
     codec = da.LiteralCodec(cfg, lay["lit_longest"])
     codec.set_block_types(ir.num_block_types)
-    res = _encode(torch, codec, lay, _tensors(torch, lay))
+    res = gh.encode_commands(torch, codec, lay, gh.to_device(torch, lay))
     codec.close(); ir.close()
     assert res["status"] == 0 and not res["flags"].any(), res["status"]
-    _assert_coded(res, streams, _code(ocfg, streams), "prefixes")
+    gh.assert_coded(res, streams, gh.oracle_bytes(ocfg, streams), "prefixes")
 
 
 FAULT_FAMILIES = [f for f in sc.FAMILIES if f.name in ("mm4_const_plain", "mm0_map_plain", "mm4_map_mix", "mmx_map_mix_nocache")]
@@ -246,7 +158,7 @@ FAULT_FAMILIES = [f for f in sc.FAMILIES if f.name in ("mm4_const_plain", "mm0_m
 def test_faulty_inputs_are_reported_and_contained(fam, sources):
     """every faulty input as the middle stream between good neighbours, one call each: the listed bit and not the other one, the flag
     on the victim alone, d_lit_sizes[victim] = 0, the victim coded as a stream without literals, the neighbours as the oracle codes
-    them, nothing written outside the slots (asserted inside _encode).  The two inputs that must pass raise nothing."""
+    them, nothing written outside the slots (asserted inside gpu_harness.encode_commands).  The two inputs that must pass raise nothing."""
     import torch
     import divans_amd as da
     g, o = fam.pair(da, po)
@@ -256,14 +168,14 @@ def test_faulty_inputs_are_reported_and_contained(fam, sources):
     at = 1
     none = sc.segments([], [], [])
     empty = po.lit_segments_encode(o, np.zeros(0, np.uint8), none["len"], none["btype"], none["last8"])
-    ref_neighbour = _code(o, [neighbour])[0]
-    codec = _codec(da, fam, g, 128)
+    ref_neighbour = gh.oracle_bytes(o, [neighbour])[0]
+    codec = gh.codec_for(da, fam, g, 128)
     for e in ce.faulty_inputs(fam, victim, sources):
         middle = dict(name=e["what"], cmds=e["cmds"], raw=e["raw"], ins=e["ins"], lit=e["lit"] if e["lit"] is not None else np.zeros(0, np.uint8),
                       segs=e["segs"] if e["segs"] is not None else sc.segments([], [], []))
         batch = [neighbour, middle, neighbour]
         lay = _lay(batch)
-        res = _encode(torch, codec, lay, _tensors(torch, lay), lit_cap=e["lit_cap"])
+        res = gh.encode_commands(torch, codec, lay, gh.to_device(torch, lay), lit_cap=e["lit_cap"])
         st, bit = res["status"], e["bit"]
         if bit:
             other = cc.BAD_SEGMENT if bit == cc.BAD_COMMAND else cc.BAD_COMMAND
@@ -271,10 +183,10 @@ def test_faulty_inputs_are_reported_and_contained(fam, sources):
             assert res["flags"].tolist() == [0, 1, 0], (e["what"], res["flags"].tolist())
             assert int(res["lit_sz"][at]) == 0, e["what"]
             assert res["coded"][at].size == empty.size and (res["coded"][at] == empty).all(), e["what"]
-            _assert_coded(res, batch, [ref_neighbour, None, ref_neighbour], e["what"], skip=(at,))
+            gh.assert_coded(res, batch, [ref_neighbour, None, ref_neighbour], e["what"], skip=(at,))
         else:
             assert st == 0 and not res["flags"].any(), (e["what"], st, res["flags"].tolist())
-            _assert_coded(res, batch, [ref_neighbour, _code(o, [middle])[0], ref_neighbour], e["what"])
+            gh.assert_coded(res, batch, [ref_neighbour, gh.oracle_bytes(o, [middle])[0], ref_neighbour], e["what"])
     codec.close()
 
 
@@ -289,12 +201,12 @@ def test_insert_command_without_insert_bytes_is_a_bad_command(sources):
     plain = cc.Stream("no_inserts", fam, sc._Data(sources, rng), rng).lit(20).copy(9, 4).lit(7).done()
     batch = [plain, victim, plain]
     lay = _lay(batch)
-    codec = _codec(da, fam, g, 64)
-    res = _encode(torch, codec, lay, _tensors(torch, lay), with_ins=False)
+    codec = gh.codec_for(da, fam, g, 64)
+    res = gh.encode_commands(torch, codec, lay, gh.to_device(torch, lay), with_ins=False)
     codec.close()
     assert res["status"] == cc.BAD_COMMAND and res["flags"].tolist() == [0, 1, 0] and int(res["lit_sz"][1]) == 0, (res["status"], res["flags"].tolist())
-    ref = _code(o, [plain])[0]
-    _assert_coded(res, batch, [ref, None, ref], "no insert bytes", skip=(1,))
+    ref = gh.oracle_bytes(o, [plain])[0]
+    gh.assert_coded(res, batch, [ref, None, ref], "no insert bytes", skip=(1,))
 
 
 def test_refusals(sources):
@@ -304,10 +216,10 @@ def test_refusals(sources):
     g, o = fam.pair(da, po)
     victim, neighbour = cc.victim_base(fam, sources)
     lay = _lay([neighbour, victim])
-    t = _tensors(torch, lay)
-    codec = _codec(da, fam, g, 64)
+    t = gh.to_device(torch, lay)
+    codec = gh.codec_for(da, fam, g, 64)
     L, h = codec._lib, codec._h
-    outs = _outputs(torch, codec, 2)
+    outs = gh.encode_outputs(codec, 2)
     lit_sz = torch.zeros(2, dtype=torch.int32, device=t["raw"].device)
     args = [t["raw"], t["raw_off"], t["raw_sz"], 2, t["cmd_begin"], t["cmds"], 64, t["ins"], t["ins_off"], t["ins_sz"], outs["out"], outs["slot"], outs["offsets"],
             outs["sizes"], lit_sz]

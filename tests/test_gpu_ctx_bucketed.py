@@ -9,14 +9,13 @@ import numpy as np
 import pytest
 
 import bucketed_segment_cases as bc
+import gpu_harness as gh
 import ctx_bucketed_cases as cc
 import irtext
 import pyoracle as po
 import segment_cases as sc
-from test_gpu_bucketed_segments import _assert_same, _encode, _ir_streams, _oracle, _split, _tensors
 
 pytestmark = pytest.mark.gpu
-BAD_SEGMENT = 4
 KEYS = list(cc.FAMILIES)
 LENGTHS = [1, 2, 63, 64, 65, 8191, 8192, 8193, 16385, 40000, 65535, 65536]
 _CASES = {}
@@ -34,14 +33,8 @@ def _case(key, sources):
         fam = cc.FAMILIES[key]
         g, o = fam.pair(da, po)
         streams = cc.batch(fam, sources)
-        _CASES[key] = (fam, g, o, streams, _oracle(o, streams))
+        _CASES[key] = (fam, g, o, streams, gh.oracle_bytes(o, streams))
     return _CASES[key]
-
-
-def _codec(da, fam, g, longest):
-    codec = da.LiteralCodec(g, max(longest, 16))
-    codec.set_block_types(fam.n_btypes)
-    return codec
 
 
 @pytest.mark.parametrize("key", KEYS)
@@ -53,28 +46,28 @@ def test_path_2_accepts_context_keyed_rows(key, sources):
     fam, g, o, streams, coded = _case(key, sources)
     few = [s for s in streams if s[1].size <= 4000][:12]
     ref = [coded[k] for k, s in enumerate(streams) if s[1].size <= 4000][:12]
-    tin = _tensors(torch, few)
+    tin = gh.ragged_tensors(torch, few)
     codec = da.LiteralCodec(g, max(tin["longest"], 16))
     codec.set_encode_path(2)
     codec.set_block_types(fam.n_btypes)
     codec.set_encode_path(0)
     codec.set_encode_path(2)
     assert codec.last_encode_path() == 0
-    st, got, path = _encode(codec, tin)
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == cc.BUCKETED_PATH[key], (st, path)
-    _assert_same(got, ref, few, "path 2")
+    gh.assert_same(got, ref, few, "path 2")
     codec.set_encode_path(0)          # automatic: a list stays on the streaming kernels, a call without one takes the bucketed pass
-    st, got, path = _encode(codec, tin)
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, ref, few, "automatic")
+    gh.assert_same(got, ref, few, "automatic")
     outs = codec.alloc_encode_outputs(tin["n"])
     codec.encode_batch(tin["lit"], tin["n"], tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
     assert codec.status() == 0 and codec.last_encode_path() == cc.BUCKETED_PATH[key]
-    auto = _split(tin, outs)
+    auto = gh.split_outputs(outs, tin["n"])
     codec.set_encode_path(1)
     codec.encode_batch(tin["lit"], tin["n"], tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
     assert codec.status() == 0 and codec.last_encode_path() == 1
-    for i, (a, b) in enumerate(zip(auto, _split(tin, outs))):
+    for i, (a, b) in enumerate(zip(auto, gh.split_outputs(outs, tin["n"]))):
         assert a.size == b.size and (a == b).all(), f"automatic without a list: stream {i} ({few[i][0]})"
     codec.close()
 
@@ -84,7 +77,7 @@ def test_a_constant_context_stays_refused(name):
     import divans_amd as da
     fam = next(f for f in sc.FAMILIES if f.name == name)
     g, _ = fam.pair(da, po)
-    codec = _codec(da, fam, g, 4096)
+    codec = gh.codec_for(da, fam, g, 4096)
     with pytest.raises(da.DivansGpuError, match="bucketed encoder needs"):
         codec.set_encode_path(2)
     codec.close()
@@ -95,20 +88,20 @@ def test_context_keyed_pass_codes_segment_lists_bit_exact(key, sources):
     import torch
     import divans_amd as da
     fam, g, o, streams, coded = _case(key, sources)
-    tin = _tensors(torch, streams)
+    tin = gh.ragged_tensors(torch, streams)
     assert tin["longest"] == 65536 and tin["n"] == 47
-    codec = _codec(da, fam, g, tin["longest"])
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     codec.set_encode_path(2)
     for what, sub in (("one launch sequence", None), ("launch sequences of 24 streams", 24)):
         if sub:
             codec.set_bucket_batch(sub)
-        st, got, path = _encode(codec, tin)
+        st, got, path = gh.encode_segments(codec, tin)
         assert st == 0 and path == cc.BUCKETED_PATH[key], (what, st, path)
-        _assert_same(got, coded, streams, what)
+        gh.assert_same(got, coded, streams, what)
     codec.set_encode_path(1)
-    st, got, path = _encode(codec, tin)
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, coded, streams, "streaming kernels")
+    gh.assert_same(got, coded, streams, "streaming kernels")
     codec.close()
 
 
@@ -131,18 +124,18 @@ def test_context_keyed_pass_over_prediction_modes(mode, mix, sources):
         lens = sc._cut(L, cuts)
         starts = [0] + cuts
         streams.append((f"M{k}", lit.copy(), sc.segments(lens, (np.arange(len(lens)) + k) % 2, bc._last8s(rng, lit, starts))))
-    coded = _oracle(o, streams)
-    tin = _tensors(torch, streams)
+    coded = gh.oracle_bytes(o, streams)
+    tin = gh.ragged_tensors(torch, streams)
     codec = da.LiteralCodec(g, L)
     codec.set_block_types(2)
     codec.set_encode_path(2)
-    st, got, path = _encode(codec, tin)
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == (3 if mix else 2), (st, path)
-    _assert_same(got, coded, streams, f"mode {mode}")
+    gh.assert_same(got, coded, streams, f"mode {mode}")
     outs = codec.alloc_encode_outputs(tin["n"])       # and without the lists: block type 0 throughout
     codec.encode_batch(tin["lit"], tin["n"], L, outs, in_offsets=tin["off"], in_sizes=tin["sz"])
     assert codec.status() == 0 and codec.last_encode_path() == (3 if mix else 2)
-    for i, (a, lit) in enumerate(zip(_split(tin, outs), blocks)):
+    for i, (a, lit) in enumerate(zip(gh.split_outputs(outs, tin["n"]), blocks)):
         b = po.lit_encode(o, lit)
         assert a.size == b.size and (a == b).all(), (mode, mix, i)
     codec.close()
@@ -166,7 +159,7 @@ def test_context_keyed_pass_without_a_list(n, key, sources):
     outs = codec.alloc_encode_outputs(len(blocks))
     codec.encode_batch(t(buf), len(blocks), n, outs, in_offsets=t(offs), in_sizes=t(sizes))
     assert codec.status() == 0 and codec.last_encode_path() == cc.BUCKETED_PATH[key]
-    got = _split(dict(n=len(blocks)), outs)
+    got = gh.split_outputs(outs, len(blocks))
     for i, (a, lit) in enumerate(zip(got, blocks)):
         b = po.lit_encode(o, lit)
         assert a.size == b.size and (a == b).all(), (n, key, i)
@@ -188,16 +181,16 @@ def test_faulty_lists_are_reported_by_the_context_keyed_pass(key, sources):
     assert good[3][0] == "X_span"
     batches.append(("block type outside the tables, on the segment that covers pieces 3 to 5", bc.bad_btype(good, 3, 200, 3), (3,)))
     batches.append(("empty stream, list of 5 bytes", bc.empty_stream_with_bytes_in_its_list(good, 4), (4,)))
-    tins = [_tensors(torch, batch) for _, batch, _ in batches]
-    codec = _codec(da, fam, g, max(t["longest"] for t in tins))
+    tins = [gh.ragged_tensors(torch, batch) for _, batch, _ in batches]
+    codec = gh.codec_for(da, fam, g, max(t["longest"] for t in tins))
     codec.set_encode_path(2)
     for (what, batch, skip), tin in zip(batches, tins):
-        st, got, path = _encode(codec, tin)
-        assert st & BAD_SEGMENT and path == cc.BUCKETED_PATH[key], (what, st, path)
-        _assert_same(got, coded, batch, what, skip=skip)
-    st, got, path = _encode(codec, _tensors(torch, good))
+        st, got, path = gh.encode_segments(codec, tin)
+        assert st & gh.BAD_SEGMENT and path == cc.BUCKETED_PATH[key], (what, st, path)
+        gh.assert_same(got, coded, batch, what, skip=skip)
+    st, got, path = gh.encode_segments(codec, gh.ragged_tensors(torch, good))
     assert st == 0 and path == cc.BUCKETED_PATH[key], (st, path)
-    _assert_same(got, coded, good, "the same streams with their lists in order")
+    gh.assert_same(got, coded, good, "the same streams with their lists in order")
     codec.close()
 
 
@@ -211,7 +204,7 @@ def test_real_command_lists_under_their_own_context_maps(name, mixing):
     import torch
     import divans_amd as da
     ir = da.CommandIR(irtext.load_ir_text(name))
-    streams = _ir_streams(ir, 32)
+    streams = gh.ir_streams(ir, 32)
     assert len(streams) >= 8 and all(0 < s[1].size <= 65536 for s in streams) and any(s[2].size > 1 for s in streams)
     cfg = ir.lit_config(dynamic_context_mixing=mixing, use_context_map=1)
     assert set(bytes(cfg.mixing_mask)) == {0}            # uniformly 0: no mixing-value-4 pass can be what runs below
@@ -219,8 +212,8 @@ def test_real_command_lists_under_their_own_context_maps(name, mixing):
     constant = len(set(cmap.tolist())) == 1
     assert constant == (name == "alice29-q11")
     ocfg = po.LitConfig.from_buffer_copy(bytes(cfg))
-    coded = _oracle(ocfg, streams)
-    tin = _tensors(torch, streams)
+    coded = gh.oracle_bytes(ocfg, streams)
+    tin = gh.ragged_tensors(torch, streams)
     codec = da.LiteralCodec(cfg, max(tin["longest"], 16))
     codec.set_block_types(ir.num_block_types)
     if constant:
@@ -229,14 +222,9 @@ def test_real_command_lists_under_their_own_context_maps(name, mixing):
     else:
         codec.set_encode_path(2)
     outs = codec.alloc_encode_outputs(tin["n"])
-    st, got, path = _encode(codec, tin, outs)
+    st, got, path = gh.encode_segments(codec, tin, outs)
     assert st == 0 and path == (1 if constant else 3 if mixing else 2), (st, path)
-    _assert_same(got, coded, streams, name)
-    back = torch.zeros_like(tin["lit"])
-    codec.decode_segments_batch(outs["out"], outs["offsets"], outs["sizes"], tin["n"], tin["longest"], tin["sb"], tin["segs"], back, tin["off"], tin["sz"])
-    assert codec.status() == 0
-    back = back.cpu().numpy()
-    for (nm, lit, _), off in zip(streams, tin["offs"]):
-        assert (back[int(off):int(off) + lit.size] == lit).all(), (name, nm)
+    gh.assert_same(got, coded, streams, name)
+    gh.assert_round_trip_segments(torch, codec, tin, outs, streams, name)
     codec.close()
     ir.close()

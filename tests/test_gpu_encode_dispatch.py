@@ -10,53 +10,12 @@ import numpy as np
 import pytest
 
 import bucketed_segment_cases as bc
-import ctx_bucketed_cases as cx
-import mix_bt_bucketed_cases as mb
+import gpu_harness as gh
 import pyoracle as po
 import segment_cases as sc
-import stride_bucketed_cases as stc
-from test_gpu_bucketed_segments import _assert_same, _encode, _oracle, _split, _tensors
+from encode_dispatch_cases import TABLE, WRAP_SPEED
 
 pytestmark = pytest.mark.gpu
-WRAP_SPEED = (0x7800, 0x7800)       # a row's total leaves i16 at its second update
-
-
-def _sc(name):
-    return next(f for f in sc.FAMILIES if f.name == name)
-
-
-class Row:
-    """family: the configuration.  types: what set_block_types is given (None: the codec stays as created, tables for the
-    configuration's own block type).  accepted: set_encode_path(2) succeeds.  ran: last_encode_path() after a call without a list and
-    after one with a list, for the paths 0, 1 and 2 -- where path 2 is refused the codec keeps path 1, which it was given before.
-    wrap: WRAP_SPEED in every slot.  path_2_before_types: path 2 is asked for (and accepted) on the codec as created, then the block
-    types are set and the table is walked."""
-
-    def __init__(self, family, types, accepted, ran, wrap=False, path_2_before_types=False):
-        self.family, self.types, self.accepted, self.ran, self.wrap, self.path_2_before_types = family, types, accepted, ran, wrap, path_2_before_types
-
-
-def _bucketed(p):
-    return {0: (p, 1), 1: (1, 1), 2: (p, p)}
-
-
-STREAMING = {0: (1, 1), 1: (1, 1), 2: (1, 1)}
-TABLE = {
-    "stride_1": Row(bc.CONFIGS["A"], 8, True, _bucketed(2)),
-    "stride_3": Row(stc.FAMILIES["m6"], 8, True, _bucketed(2)),
-    "two_model": Row(bc.CONFIGS["C"], 1, True, _bucketed(3)),
-    "context_keyed": Row(cx.FAMILIES["plain"], 8, True, _bucketed(2)),
-    "context_keyed_two_model": Row(cx.FAMILIES["mix"], 8, True, _bucketed(3)),
-    "two_model_block_types": Row(mb.FAMILIES["u2"], 2, True, _bucketed(3)),
-    # mixing value 0 under a constant context: one bucket per stream, no pass
-    "no_pass": Row(_sc(cx.REFUSED[0]), 8, False, STREAMING),
-    # the stride-1 pass exists, so path 2 is accepted; every call runs the streaming kernels, which watch for wrapped rows
-    "stride_1_wrap_checked": Row(bc.CONFIGS["A"], 8, True, STREAMING, wrap=True),
-    # mixing value 4 with a map and two models: the two-model pass while the codec keeps one block type's tables; with all eight a
-    # previous byte reaches 31 contexts (mix_bt_bucketed_cases.REFUSED) and no pass is left, whatever path was accepted before
-    "two_model_as_created": Row(_sc("mm4_map_mix"), None, True, _bucketed(3)),
-    "two_model_then_8_types": Row(_sc("mm4_map_mix"), 8, False, STREAMING, path_2_before_types=True),
-}
 _CASES = {}
 
 
@@ -88,7 +47,7 @@ def _case(key, corpus):
                 for i in range(4):
                     cfg.literal_adaptation[i].inc, cfg.literal_adaptation[i].lim = WRAP_SPEED
         streams = _streams(row, corpus)
-        with_list = _oracle(o, streams)
+        with_list = gh.oracle_bytes(o, streams)
         without = [po.lit_encode(o, lit) for _, lit, _ in streams]
         if row.wrap:    # the premise: the oracle reads its own bytes back, so no wrapped row was coded with
             for (_, lit, s), a, b in zip(streams, with_list, without):
@@ -104,7 +63,7 @@ def test_the_pass_a_call_runs(key, corpus):
     row = TABLE[key]
     g, streams, with_list, without = _case(key, corpus)
     assert len(streams) == 3 and max(s[1].size for s in streams) <= 300
-    tin = _tensors(torch, streams)
+    tin = gh.ragged_tensors(torch, streams)
     codec = da.LiteralCodec(g, max(tin["longest"], 16))
     if row.path_2_before_types:
         codec.set_encode_path(2)
@@ -115,7 +74,7 @@ def test_the_pass_a_call_runs(key, corpus):
     if row.path_2_before_types:     # the path accepted earlier is still set: with no pass left the call runs the streaming kernels
         codec.encode_batch(tin["lit"], tin["n"], tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
         assert codec.status() == 0 and codec.last_encode_path() == 1
-        _assert_same(_split(tin, outs), without, streams, f"{key}, the path 2 of before the block types")
+        gh.assert_same(gh.split_outputs(outs, tin["n"]), without, streams, f"{key}, the path 2 of before the block types")
     for path in (0, 1, 2):
         if path < 2 or row.accepted:
             codec.set_encode_path(path)
@@ -126,8 +85,8 @@ def test_the_pass_a_call_runs(key, corpus):
         codec.encode_batch(tin["lit"], tin["n"], tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
         st, ran = codec.status(), codec.last_encode_path()
         assert st == 0 and ran == no_list, (key, path, "no list", st, ran)
-        _assert_same(_split(tin, outs), without, streams, f"{key}, path {path}, no list")
-        st, got, ran = _encode(codec, tin, outs)
+        gh.assert_same(gh.split_outputs(outs, tin["n"]), without, streams, f"{key}, path {path}, no list")
+        st, got, ran = gh.encode_segments(codec, tin, outs)
         assert st == 0 and ran == listed, (key, path, "two-segment lists", st, ran)
-        _assert_same(got, with_list, streams, f"{key}, path {path}, two-segment lists")
+        gh.assert_same(got, with_list, streams, f"{key}, path {path}, two-segment lists")
     codec.close()

@@ -19,10 +19,11 @@ import pytest
 import bucketed_segment_cases as bc
 import command_cases as cc
 import ctx_bucketed_cases as cx
+import encode_dispatch_cases as ed
 import far_offset_cases as fo
+import gpu_harness as gh
 import pyoracle as po
 import segment_cases as sc
-import test_gpu_encode_dispatch as ed
 
 pytestmark = pytest.mark.gpu
 G31, G32 = fo.G31, fo.G32
@@ -134,12 +135,6 @@ def _image(lay, real, decoy):
     return fo.image(lay, real, decoy)
 
 
-def _same(got, want, what):
-    assert len(got) == len(want)
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert g.size == w.size and (g == w).all(), f"{what}: stream {i} ({w.size} bytes) differs"
-
-
 def _two_segments(streams, btype, seed):
     """a two-segment list per stream, the second under a context that is not the natural one"""
     rng = np.random.default_rng(seed)
@@ -183,13 +178,8 @@ def _read_slots(slots, outs, want, what):
     assert got_off == offs, (what, "d_out_offsets: not right-aligned in the far slots", got_off, offs)
     got = [slots.get(o, s) for o, s in zip(offs, sizes)]
     slots.untouched_outside(windows, what)
-    _same(got, want, what)
+    gh.assert_same(got, want, None, what)
     return got
-
-
-def _read_near(outs, n=8):
-    out = outs["out"].cpu().numpy(); offs = outs["offsets"].cpu().numpy(); sz = outs["sizes"].cpu().numpy()
-    return [out[int(offs[i]):int(offs[i]) + int(sz[i])] for i in range(n)]
 
 
 ENCODE_ROWS = [k for k, r in ed.TABLE.items() if r.accepted and not r.wrap and not r.path_2_before_types]
@@ -197,7 +187,7 @@ ENCODE_ROWS = [k for k, r in ed.TABLE.items() if r.accepted and not r.wrap and n
 
 @pytest.mark.parametrize("key", ENCODE_ROWS)
 def test_encoders_read_far_input_and_write_far_slots(key, pair):
-    """encode_batch, encode_batch_chunks and encode_segments_batch on a row of test_gpu_encode_dispatch.TABLE, under the streaming
+    """encode_batch, encode_batch_chunks and encode_segments_batch on a row of encode_dispatch_cases.TABLE, under the streaming
     kernels and the row's bucketed pass, on a codec for short streams (one rANS lane per stream) and on one above 32 768 bytes (one
     lane per chunk, two lanes per chunk, the stitch)"""
     import torch
@@ -241,9 +231,9 @@ def test_encoders_read_far_input_and_write_far_slots(key, pair):
                     nouts = codec.alloc_encode_outputs(8)
                     st, p = call(entry, nouts, _d(near.offsets, np.int64))
                     assert st == 0 and p == expect_path[entry], (what, "near", st, p)
-                    control = _read_near(nouts)
+                    control = gh.split_outputs(nouts, 8)
                     control_chunks = chunks.cpu().numpy().copy()
-                    _same(control, want[entry], what + ", near offsets")
+                    gh.assert_same(control, want[entry], None, what + ", near offsets")
                     for lay in lays:
                         src.put(_image(lay, real, decoy))
                         outs = _slot_outputs(torch, slots)
@@ -251,7 +241,7 @@ def test_encoders_read_far_input_and_write_far_slots(key, pair):
                         where = f"{what}, input at {sorted(lay.anchored)}"
                         assert st == 0 and p == expect_path[entry], (where, st, p)
                         got = _read_slots(slots, outs, want[entry], where)
-                        _same(got, control, where + " against the near call")
+                        gh.assert_same(got, control, None, where + " against the near call")
                         if entry == "chunks":
                             assert (chunks.cpu().numpy() == control_chunks).all() and (control_chunks.sum(axis=1) == [w.size for w in want[entry]]).all(), where
                     ran.add((msl, path, entry, p, split))
@@ -298,7 +288,7 @@ def test_model_batch_and_encode_packed_read_far_input(cfg_name, pair):
             ran.add(("encode_packed", path, codec.last_encode_path()))
             assert psz.cpu().tolist() == [w.size for w in want] and poff.cpu().tolist() == ref_off.tolist() and int(total.item()) == ref_total, what
             got = packed.cpu().numpy()
-            _same([got[a:a + w.size] for a, w in zip(ref_off, want)], want, what + ", encode_packed")
+            gh.assert_same([got[a:a + w.size] for a, w in zip(ref_off, want)], want, None, what + ", encode_packed")
             assert (got[ref_total:] == fo.SENTINEL).all(), what
     codec.close()
     print(cfg_name, "ran (entry, path asked, pass):", sorted(ran))
@@ -379,10 +369,10 @@ def test_encode_commands_batch_reads_far_raw_and_insert_bytes(sources):
             assert lit_sz.cpu().tolist() == [s["lit"].size for s in streams], what
             if far:
                 got = _read_slots(slots, outs, want, what)
-                _same(got, control, what + " against the near call")
+                gh.assert_same(got, control, None, what + " against the near call")
             else:
-                control = _read_near(outs)
-                _same(control, want, what)
+                control = gh.split_outputs(outs, 8)
+                gh.assert_same(control, want, None, what)
     codec.close()
     _drop("in2")
     print("encode_commands_batch ran (path asked, pass):", sorted(ran))
@@ -394,7 +384,7 @@ def _read_out(out, offsets, want, what):
     windows = [(fo.FRONT + o, w.size) for o, w in zip(offsets, want) if w.size]
     got = [out.get(o, w.size) for o, w in zip(offsets, want)]
     out.untouched_outside(windows, what)
-    _same(got, want, what)
+    gh.assert_same(got, want, None, what)
 
 
 def _paired(a, b):
@@ -535,7 +525,7 @@ def test_row_replay_reads_far_literals(pair):
     codec.decode_batch(src.r, _d(lay.offsets, np.int64), _d(csz, np.int32), 8, longest, back, out_offsets=_d(rl.offsets, np.int64), out_sizes=sizes)
     assert codec.status() == 0
     back = back.cpu().numpy()
-    _same([back[a:a + s.size] for a, s in zip(rl.offsets, real)], real, "decode after row_replay")
+    gh.assert_same([back[a:a + s.size] for a, s in zip(rl.offsets, real)], real, None, "decode after row_replay")
     codec.close()
 
 
@@ -569,7 +559,7 @@ def test_byte_order_is_learned_from_a_batch_wholly_above_4g(pair):
     assert codec.status() == 0
     bo = codec.byte_order(with_rank=True)
     assert bo["ready"] and bo["rank"] == expect, (sorted(range(256), key=lambda b: bo["rank"][b])[:8], order[:8])
-    _same(_read_near(outs, n), _oracle(o, real), "the batch above 2^32")
+    gh.assert_same(gh.split_outputs(outs, n), _oracle(o, real), None, "the batch above 2^32")
     codec.close()
 
 

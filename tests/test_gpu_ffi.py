@@ -16,17 +16,12 @@ from ffi_harness import CAllocator, OPTION_SETS
 import ffi_harness
 
 
-def _lib():
-    import divans_amd as da
-    return ffi_harness.bind(da.load_library())
-
-
 def ffi_compress(data, options, **kw):
-    return ffi_harness.ffi_compress(_lib(), data, options, **kw)
+    return ffi_harness.ffi_compress(ffi_harness.product_library(), data, options, **kw)
 
 
 def ffi_decompress(coded, expect_len, **kw):
-    return ffi_harness.ffi_decompress(_lib(), coded, expect_len, **kw)
+    return ffi_harness.ffi_decompress(ffi_harness.product_library(), coded, expect_len, **kw)
 
 
 @pytest.mark.parametrize("which", range(len(OPTION_SETS)))
@@ -59,7 +54,7 @@ def test_window_split_and_small_buffers(corpus):
 
 
 def test_option_errors():
-    L = _lib()
+    L = ffi_harness.product_library()
     st = L.divans_new_compressor()
     assert L.divans_set_option(st, 99, 1) == 3                 # unknown selector
     assert L.divans_set_option(st, 9, 9) == 3                  # stride out of range (compressor.rs:96-108)
@@ -102,7 +97,7 @@ def test_default_options_encode_literal_only(corpus):
 
 def test_corrupt_and_truncated_streams_fail(corpus):
     """a damaged LIT stream must not decode to garbage with DIVANS_SUCCESS."""
-    L = _lib()
+    L = ffi_harness.product_library()
     data = corpus[:40000]
     coded = ffi_compress(data, [(5, 0)]).copy()
 
@@ -201,7 +196,7 @@ def test_encoder_works_call_by_call(corpus):
     reference as here.  What does NOT accumulate any more is the input and the 8 bytes of (start, freq) per byte of it."""
     import hashlib
     import workload
-    L = _lib()
+    L = ffi_harness.product_library()
     st = L.divans_new_compressor()
     for sel, val in [(5, 0), (2, 16)]:
         assert L.divans_set_option(st, sel, val) == 0
@@ -260,7 +255,7 @@ def test_decoder_works_call_by_call(corpus):
     import workload
     data = workload.make_blocks(corpus, 31, 256).reshape(-1)              # 16 MiB
     coded = po.stream_compress_raw(data, po.stream_options(window_size=16, call_buffer_size=65536), call_inputs=[65536] * 256)
-    L = _lib()
+    L = ffi_harness.product_library()
     st = L.divans_new_decompressor()
 
     def rss():

@@ -10,15 +10,14 @@ import numpy as np
 import pytest
 
 import bucketed_segment_cases as bc
+import gpu_harness as gh
 import ctx_bucketed_cases as cc
 import irtext
 import mix_bt_bucketed_cases as mc
 import pyoracle as po
 import segment_cases as sc
-from test_gpu_bucketed_segments import _assert_same, _encode, _ir_streams, _oracle, _split, _tensors
 
 pytestmark = pytest.mark.gpu
-BAD_SEGMENT = 4
 KEYS = list(mc.FAMILIES)
 _CASES = {}
 
@@ -35,14 +34,8 @@ def _case(key, sources):
         fam = mc.FAMILIES[key]
         g, o = fam.pair(da, po)
         streams = mc.batch(fam, sources)
-        _CASES[key] = (fam, g, o, streams, _oracle(o, streams))
+        _CASES[key] = (fam, g, o, streams, gh.oracle_bytes(o, streams))
     return _CASES[key]
-
-
-def _codec(da, fam, g, longest):
-    codec = da.LiteralCodec(g, max(longest, 16))
-    codec.set_block_types(fam.n_btypes)
-    return codec
 
 
 @pytest.mark.parametrize("key", KEYS)
@@ -50,33 +43,28 @@ def test_path_2_codes_several_block_types_bit_exact(key, sources):
     import torch
     import divans_amd as da
     fam, g, o, streams, coded = _case(key, sources)
-    tin = _tensors(torch, streams)
+    tin = gh.ragged_tensors(torch, streams)
     assert tin["longest"] == 65536 and tin["n"] == 48
-    codec = _codec(da, fam, g, tin["longest"])
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     assert codec.high_row_slots() == 8
     codec.set_encode_path(2)
     outs = codec.alloc_encode_outputs(tin["n"])
     for what, sub in (("one launch sequence", None), ("launch sequences of 24 streams", 24)):
         if sub:
             codec.set_bucket_batch(sub)
-        st, got, path = _encode(codec, tin, outs)
+        st, got, path = gh.encode_segments(codec, tin, outs)
         assert st == 0 and path == mc.BUCKETED_PATH == 3, (what, st, path)
-        _assert_same(got, coded, streams, what)
-    back = torch.zeros_like(tin["lit"])
-    codec.decode_segments_batch(outs["out"], outs["offsets"], outs["sizes"], tin["n"], tin["longest"], tin["sb"], tin["segs"], back, tin["off"], tin["sz"])
-    assert codec.status() == 0
-    back = back.cpu().numpy()
-    for (nm, lit, _), off in zip(streams, tin["offs"]):
-        assert (back[int(off):int(off) + lit.size] == lit).all(), (key, nm)
+        gh.assert_same(got, coded, streams, what)
+    gh.assert_round_trip_segments(torch, codec, tin, outs, streams, key)
     codec.set_encode_path(1)
-    st, got, path = _encode(codec, tin)
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, coded, streams, "streaming kernels")
+    gh.assert_same(got, coded, streams, "streaming kernels")
     codec.set_encode_path(0)          # automatic: a list stays on the streaming kernels, as for every bucketed family
     few = streams[:12]
-    st, got, path = _encode(codec, _tensors(torch, few))
+    st, got, path = gh.encode_segments(codec, gh.ragged_tensors(torch, few))
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, coded, few, "automatic, with a list")
+    gh.assert_same(got, coded, few, "automatic, with a list")
     codec.close()
 
 
@@ -87,15 +75,15 @@ def test_more_than_eight_high_rows_stay_on_the_streaming_kernels(name, sources):
     fam, count = mc.REFUSED[name]
     g, o = fam.pair(da, po)
     streams = [s for s in sc.shapes(fam, sources) if s[1].size <= 5000][:16] + [mc.all_slots(fam)]
-    coded = _oracle(o, streams)
-    tin = _tensors(torch, streams)
-    codec = _codec(da, fam, g, tin["longest"])
+    coded = gh.oracle_bytes(o, streams)
+    tin = gh.ragged_tensors(torch, streams)
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     assert codec.high_row_slots() == count
     with pytest.raises(da.DivansGpuError, match="bucketed encoder needs"):
         codec.set_encode_path(2)
-    st, got, path = _encode(codec, tin)
+    st, got, path = gh.encode_segments(codec, tin)
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, coded, streams, "automatic")
+    gh.assert_same(got, coded, streams, "automatic")
     codec.close()
 
 
@@ -139,7 +127,7 @@ def test_path_2_without_a_list(n, sources):
     d_buf, d_offs, d_sizes = t(buf), t(offs), t(sizes)
     codec.encode_batch(d_buf, len(blocks), n, outs, in_offsets=d_offs, in_sizes=d_sizes)
     assert codec.status() == 0 and codec.last_encode_path() == mc.BUCKETED_PATH
-    got = _split(dict(n=len(blocks)), outs)
+    got = gh.split_outputs(outs, len(blocks))
     for i, (a, lit) in enumerate(zip(got, blocks)):
         b = po.lit_encode(o0, lit)
         assert a.size == b.size and (a == b).all(), (n, i)
@@ -147,7 +135,7 @@ def test_path_2_without_a_list(n, sources):
         codec.set_encode_path(path)
         codec.encode_batch(d_buf, len(blocks), n, outs, in_offsets=d_offs, in_sizes=d_sizes)
         assert codec.status() == 0 and codec.last_encode_path() == ran
-        for i, (a, b) in enumerate(zip(_split(dict(n=len(blocks)), outs), got)):
+        for i, (a, b) in enumerate(zip(gh.split_outputs(outs, len(blocks)), got)):
             assert a.size == b.size and (a == b).all(), (path, n, i)
     codec.close()
 
@@ -169,16 +157,16 @@ def test_faulty_lists_are_reported_under_several_block_types(key, sources):
     assert good[6][0] == "X_edges" and int(good[6][2]["len"][:13].sum()) == 16384
     batches.append(("block type outside the tables, in the stream's third piece", bc.bad_btype(good, 6, fam.n_btypes, 13), (6,)))
     batches.append(("empty stream, list of 5 bytes", bc.empty_stream_with_bytes_in_its_list(good, 4), (4,)))
-    tins = [_tensors(torch, batch) for _, batch, _ in batches]
-    codec = _codec(da, fam, g, max(t["longest"] for t in tins))
+    tins = [gh.ragged_tensors(torch, batch) for _, batch, _ in batches]
+    codec = gh.codec_for(da, fam, g, max(t["longest"] for t in tins))
     codec.set_encode_path(2)
     for (what, batch, skip), tin in zip(batches, tins):
-        st, got, path = _encode(codec, tin)
-        assert st & BAD_SEGMENT and path == mc.BUCKETED_PATH, (what, st, path)
-        _assert_same(got, coded, batch, what, skip=skip)
-    st, got, path = _encode(codec, _tensors(torch, good))
+        st, got, path = gh.encode_segments(codec, tin)
+        assert st & gh.BAD_SEGMENT and path == mc.BUCKETED_PATH, (what, st, path)
+        gh.assert_same(got, coded, batch, what, skip=skip)
+    st, got, path = gh.encode_segments(codec, gh.ragged_tensors(torch, good))
     assert st == 0 and path == mc.BUCKETED_PATH, (st, path)
-    _assert_same(got, coded, good, "the same streams with their lists in order")
+    gh.assert_same(got, coded, good, "the same streams with their lists in order")
     codec.close()
 
 
@@ -188,7 +176,7 @@ def test_a_real_command_list_under_its_own_four_block_types():
     import torch
     import divans_amd as da
     ir = da.CommandIR(irtext.load_ir_text("random_then_unicode"))
-    streams = _ir_streams(ir, 32)
+    streams = gh.ir_streams(ir, 32)
     assert len(streams) >= 8 and all(0 < s[1].size <= 65536 for s in streams) and any(s[2].size > 1 for s in streams)
     assert ir.num_block_types == 4 and len({int(b) for s in streams for b in s[2]["btype"]}) > 1
     cfg = ir.lit_config(dynamic_context_mixing=2, use_context_map=1)
@@ -196,21 +184,16 @@ def test_a_real_command_list_under_its_own_four_block_types():
     assert cfg.context_mixing == 2
     ocfg = po.LitConfig.from_buffer_copy(bytes(cfg))
     assert 1 < mc.high_row_slots(ocfg, 4) <= 8
-    coded = _oracle(ocfg, streams)
-    tin = _tensors(torch, streams)
+    coded = gh.oracle_bytes(ocfg, streams)
+    tin = gh.ragged_tensors(torch, streams)
     codec = da.LiteralCodec(cfg, max(tin["longest"], 16))
     codec.set_block_types(ir.num_block_types)
     assert codec.high_row_slots() == mc.high_row_slots(ocfg, 4)
     codec.set_encode_path(2)
     outs = codec.alloc_encode_outputs(tin["n"])
-    st, got, path = _encode(codec, tin, outs)
+    st, got, path = gh.encode_segments(codec, tin, outs)
     assert st == 0 and path == mc.BUCKETED_PATH, (st, path)
-    _assert_same(got, coded, streams, "random_then_unicode")
-    back = torch.zeros_like(tin["lit"])
-    codec.decode_segments_batch(outs["out"], outs["offsets"], outs["sizes"], tin["n"], tin["longest"], tin["sb"], tin["segs"], back, tin["off"], tin["sz"])
-    assert codec.status() == 0
-    back = back.cpu().numpy()
-    for (nm, lit, _), off in zip(streams, tin["offs"]):
-        assert (back[int(off):int(off) + lit.size] == lit).all(), nm
+    gh.assert_same(got, coded, streams, "random_then_unicode")
+    gh.assert_round_trip_segments(torch, codec, tin, outs, streams, "random_then_unicode")
     codec.close()
     ir.close()

@@ -11,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+import gpu_harness as gh
 import pyoracle as po
 import plain_decoder_cases as pc
 
@@ -72,28 +73,6 @@ def _case(P, corpus):
     return _CASES[P]
 
 
-def _device(torch, case):
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    buf, blank, offs, sizes = case["lit"]
-    cbuf, coffs, csizes = case["cod"]
-    return dict(lit=t(buf), blank=t(blank), off=t(offs), sz=t(sizes), coded=t(cbuf), coff=t(coffs), csz=t(csizes), n=len(sizes), longest=int(sizes.max()))
-
-
-def _decode(codec, dv):
-    back = dv["blank"].clone()
-    codec.decode_batch(dv["coded"], dv["coff"], dv["csz"], dv["n"], dv["longest"], back, out_offsets=dv["off"], out_sizes=dv["sz"])
-    return codec.status(), back.cpu().numpy(), codec.last_decode_kernel()
-
-
-def _assert_decoded(back, case, what):
-    buf, _, offs, _ = case["lit"]
-    for i, ((name, lit), off) in enumerate(zip(case["streams"], offs)):
-        got = back[int(off):int(off) + lit.size]
-        assert (got == lit).all(), f"{what}: stream {i} ({name}, {lit.size} bytes) decoded wrong from byte {int(np.argmax(got != lit))}"
-    wrong = np.flatnonzero(back != buf)
-    assert wrong.size == 0, f"{what}: sentinel byte {int(wrong[0]) if wrong.size else -1} of {buf.size} written to"
-
-
 def _cm(name):
     m = _NAME.search(name)
     assert m, name
@@ -113,17 +92,17 @@ def test_both_organisations_decode_the_oracles_bytes(P, corpus):
     import torch
     import divans_amd as da
     case = _case(P, corpus)
-    dv = _device(torch, case)
+    dv = gh.plain_device(torch, case)
     codec = _codec(da, case, one_workgroup=P == 34)
     codec.set_byte_order(2)
     assert codec.byte_order(with_rank=True)["rank"] == case["rank"]
     tagged = 17 if P == 34 else 1           # 2-way sets for a batch of several rounds, direct mapped for a resident one
     for what, mode, cm in (("by the byte order", 0, 33), ("tagged", 1, tagged), ("pinned", 2, 33), ("tagged again", 1, tagged), ("by the byte order again", 0, 33)):
         codec.set_high_row_pinning(mode)
-        st, back, name = _decode(codec, dv)
+        st, back, name = gh.decode_plain(codec, dv)
         assert st == 0, (what, st, name)
         assert _cm(name) == cm, (what, name)
-        _assert_decoded(back, case, f"P = {P}, {what}")
+        gh.assert_plain_decoded(back, case, f"P = {P}, {what}")
     # round trip: the encoder writes the oracle's bytes, whatever the decoder's organisation
     outs = codec.alloc_encode_outputs(dv["n"])
     codec.encode_batch(dv["lit"], dv["n"], dv["longest"], outs, in_offsets=dv["off"], in_sizes=dv["sz"])
@@ -140,17 +119,17 @@ def test_numeric_order_keeps_the_two_way_sets(corpus):
     import torch
     import divans_amd as da
     case = _case(34, corpus)
-    dv = _device(torch, case)
+    dv = gh.plain_device(torch, case)
     codec = _codec(da, case, one_workgroup=True)
     codec.set_byte_order(1)
     for call in range(2):
-        st, back, name = _decode(codec, dv)
+        st, back, name = gh.decode_plain(codec, dv)
         assert st == 0 and _cm(name) == 17, (call, st, name)
-        _assert_decoded(back, case, f"numeric order, call {call}")
+        gh.assert_plain_decoded(back, case, f"numeric order, call {call}")
     codec.set_high_row_pinning(2)            # forced: the byte values 0 .. 33 are pinned
-    st, back, name = _decode(codec, dv)
+    st, back, name = gh.decode_plain(codec, dv)
     assert st == 0 and _cm(name) == 33, (st, name)
-    _assert_decoded(back, case, "numeric order, pinned on request")
+    gh.assert_plain_decoded(back, case, "numeric order, pinned on request")
     codec.close()
 
 
@@ -159,16 +138,16 @@ def test_learned_order_pins_from_the_second_decode_on(corpus):
     import torch
     import divans_amd as da
     case = _case(34, corpus)
-    dv = _device(torch, case)
+    dv = gh.plain_device(torch, case)
     codec = _codec(da, case, one_workgroup=True)
     assert codec.byte_order() == {"mode": 0, "ready": False}
     for call, cm in enumerate((17, 33, 33)):
-        st, back, name = _decode(codec, dv)
+        st, back, name = gh.decode_plain(codec, dv)
         assert st == 0 and _cm(name) == cm, (call, st, name)
-        _assert_decoded(back, case, f"learned order, call {call}")
+        gh.assert_plain_decoded(back, case, f"learned order, call {call}")
         assert codec.byte_order()["ready"]
     codec.set_decoder(3)                     # a caller who chooses an organisation keeps it
-    st, back, name = _decode(codec, dv)
+    st, back, name = gh.decode_plain(codec, dv)
     assert st == 0 and _cm(name) == 17, (st, name)
-    _assert_decoded(back, case, "2-way on request")
+    gh.assert_plain_decoded(back, case, "2-way on request")
     codec.close()

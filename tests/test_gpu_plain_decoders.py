@@ -18,6 +18,7 @@ import re
 import numpy as np
 import pytest
 
+import gpu_harness as gh
 import plain_decoder_cases as pc
 import pyoracle as po
 import segment_cases as sc
@@ -63,31 +64,6 @@ def _codec(da, fam, case):
     return codec
 
 
-def _device(torch, case):
-    dev = torch.device("cuda")
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    buf, blank, offs, sizes = case["lit"]
-    cbuf, coffs, csizes = case["cod"]
-    return dict(lit=t(buf), blank=t(blank), off=t(offs), sz=t(sizes), coded=t(cbuf), coff=t(coffs), csz=t(csizes), n=len(sizes), longest=int(sizes.max()))
-
-
-def _decode(codec, dv):
-    """-> (status, the whole output buffer, name of the kernel that ran)"""
-    back = dv["blank"].clone()
-    codec.decode_batch(dv["coded"], dv["coff"], dv["csz"], dv["n"], dv["longest"], back, out_offsets=dv["off"], out_sizes=dv["sz"])
-    st = codec.status()
-    return st, back.cpu().numpy(), codec.last_decode_kernel()
-
-
-def _assert_decoded(back, case, what):
-    buf, _, offs, _ = case["lit"]
-    for i, ((name, lit), off) in enumerate(zip(case["streams"], offs)):
-        got = back[int(off):int(off) + lit.size]
-        assert (got == lit).all(), f"{what}: stream {i} ({name}, {lit.size} bytes, {case['coded'][i].size // 4} coded words) decoded wrong from byte {int(np.argmax(got != lit))}"
-    wrong = np.flatnonzero(back != buf)
-    assert wrong.size == 0, f"{what}: sentinel byte {int(wrong[0]) if wrong.size else -1} of {buf.size} written to"
-
-
 def _assert_kernel(fam, what, name, cmv=None):
     """lit_decode2_kernel_*<MM, CTXC, MIX, false, CMV>; cmv None: non-zero exactly when the family's table admits row caches"""
     m = _NAME.search(name)
@@ -121,9 +97,8 @@ def test_decode_oracle_bytes_on_every_cache_set(fam, sources):
     chain.  No row cache exists above 32 766 rows per stream: there set_decoder refuses rows and only the launches without run."""
     import torch
     import divans_amd as da
-    import test_gpu_segment_cases as seg
     case = _case(fam, sources)
-    dv = _device(torch, case)
+    dv = gh.plain_device(torch, case)
     for gen in (2, 3):
         assert gen in da.decoder_generations()
         codec = _codec(da, fam, case)
@@ -134,22 +109,22 @@ def test_decode_oracle_bytes_on_every_cache_set(fam, sources):
             codec = _codec(da, fam, case)      # (the refused call has already left the library's choice of organisation)
         for what, setup, cmv in _generation_chain(da, fam, gen):
             setup(codec)
-            st, back, name = _decode(codec, dv)
+            st, back, name = gh.decode_plain(codec, dv)
             assert st == 0, (what, st, name)
             _assert_kernel(fam, what, name, cmv)
-            _assert_decoded(back, case, what)
+            gh.assert_plain_decoded(back, case, what)
         codec.close()
-    for chain in seg._decoder_chains(da, fam):
+    for chain in gh.decoder_chains(da, fam):
         if chain[0][2] != 1:
             continue
         codec = _codec(da, fam, case)
         for what, setup, _ in chain:
             setup(codec)
-            st, back, name = _decode(codec, dv)
+            st, back, name = gh.decode_plain(codec, dv)
             assert st == 0, (what, st, name)
             cache = 2 if fam.cached and "no cache" not in what else 0
-            assert f"lit_decode_kernel<{fam.mm if fam.mm >= 0 else -1}, {seg._b(fam.ctxc)}, {seg._b(fam.mix)}, {cache}, false>" in name, (what, name)
-            _assert_decoded(back, case, what)
+            assert f"lit_decode_kernel<{fam.mm if fam.mm >= 0 else -1}, {gh.tf(fam.ctxc)}, {gh.tf(fam.mix)}, {cache}, false>" in name, (what, name)
+            gh.assert_plain_decoded(back, case, what)
         codec.close()
     _RAN.add(fam.name)
 
@@ -178,7 +153,7 @@ def test_encoders_write_the_oracles_bytes(fam, sources):
     import torch
     import divans_amd as da
     case = _case(fam, sources)
-    dv = _device(torch, case)
+    dv = gh.plain_device(torch, case)
     codec = _codec(da, fam, case)
     codec.set_geometry(blocks=2)
     for ask in (1, 2):

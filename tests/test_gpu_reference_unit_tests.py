@@ -21,15 +21,13 @@ import numpy as np
 import pytest
 
 import cdf_ops_sweeps as sw
+import gpu_harness as gh
 import pyoracle as po
 import ref_restatement as rr
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-MED, SLOW, MUD = (0x30, 0x4000), (0x20, 0x1000), (0x10, 0x2000)
-BUF0 = [0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 5, 5, 5, 5, 5, 6, 7, 8, 8, 9, 9, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 11, 12, 12, 12, 13, 13, 13, 14, 15,
-        15, 15, 15, 15, 15, 15]
-BUF1 = [0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 5, 5, 5, 5, 5]
+MED, SLOW = sw.MED, sw.SLOW
 
 
 @pytest.fixture(scope="module")
@@ -40,15 +38,7 @@ def codec():
     c.close()
 
 
-def implementations():
-    """the device's restatements of the CDF arithmetic this build can run a script on (include/divans_gpu.h,
-    divans_gpu_selftest_cdf_ops_on): generation 1, lit_decode2.hip, the bucketed encoder passes, and in experiment builds
-    lit_decode_t.hip"""
-    import divans_amd as da
-    return [0, 1, 2] + ([3] if da.experimental_decoders() else [])
-
-
-IMPLS = implementations()
+IMPLS = gh.implementations()
 
 
 def run_both(codec, impl, ops):
@@ -62,24 +52,9 @@ def run_both(codec, impl, ops):
     return got
 
 
-def script_operation_test_helper():
-    Q = 1 << 15
-    ops = []
-    for s in [3, 3, 9, 14, 0, 15, 7, 7, 7, 2] * 3:       # give row 1 a shape of its own (the reference leaves it at the default)
-        ops.append((1, s, *SLOW))
-    for s in BUF0:
-        ops.append((0, s, *MED))
-    ops.append((2, Q >> 2, 0, 0))
-    for s in BUF1:
-        ops.append((7, s, *MED))                          # the pipelined kernels' blend variant must agree too
-    for rate in (Q >> 2, Q >> 1, (Q >> 1) + (Q >> 2), 0, Q):
-        ops.append((2, rate, 0, 0))
-    return ops
-
-
 @pytest.mark.parametrize("impl", IMPLS)
 def test_operation_test_helper_on_the_device_primitives(codec, impl):
-    ops = script_operation_test_helper()
+    ops = sw.script_operation_test_helper()
     got = run_both(codec, impl, ops)
     # assert_cdf_similar(average(.., all), cdf0) / (average(.., 0), cdf1): within max0*max1/160 after cross-scaling (common_tests.rs:128-150)
     r0, r1 = got[len(ops) - 6], got[29]
@@ -88,16 +63,9 @@ def test_operation_test_helper_on_the_device_primitives(codec, impl):
         assert all(abs(int(rec[i]) * m1 - int(ref[i]) * m0) < m0 * m1 // 160 for i in range(16))
 
 
-def script_declare_common_tests():
-    ops = [(0, (i * 7 + 3) & 15, *MED) for i in range(100)]
-    ops += [(3, s, 0, 0) for s in range(16)]
-    ops += [(4, off, 0, 0) for off in range(0, 1 << 15, 1)]
-    return ops
-
-
 @pytest.mark.parametrize("impl", IMPLS)
 def test_declare_common_tests_invariants(codec, impl):
-    ops = script_declare_common_tests()
+    ops = sw.script_declare_common_tests()
     got = run_both(codec, impl, ops)
     sf = got[100:116]
     for s in range(1, 16):                                 # common_tests.rs:14-17
@@ -108,47 +76,16 @@ def test_declare_common_tests_invariants(codec, impl):
     assert ((offs >= dec[:, 0] - 1) & (offs <= dec[:, 0] + dec[:, 1])).all()
 
 
-def script_lcg_sample_run():
-    # simple_rand, common_tests.rs:44-48 (seed 1): x = x * 1103515245 + 12345; symbols drawn from a fixed pdf through a prefix table
-    x = 1
-    pdf = [0.1, 0.01, 0.03, 0.2, 0.02, 0.05, 0.04, 0.15, 0.01, 0.06, 0.03, 0.07, 0.02, 0.1, 0.08, 0.03]
-    edges = np.cumsum(pdf)
-    ops = []
-    for _ in range(60000):
-        x = (x * 1103515245 + 12345) & 0xFFFFFFFF
-        u = ((x >> 16) & 0x7FFF) / 32768.0
-        ops.append((0, int(np.searchsorted(edges, u, side="right").clip(0, 15)), *MED))
-    ops += [(0, 15, *MED)] * 30000                         # common_tests.rs:94-103
-    return ops
-
-
 @pytest.mark.parametrize("impl", IMPLS)
 def test_lcg_sample_run_and_symbol_15_stress(codec, impl):
-    got = run_both(codec, impl, script_lcg_sample_run())
+    got = run_both(codec, impl, sw.script_lcg_sample_run())
     final = got[-1]
     assert (np.diff(np.concatenate([[0], final])) > 0).all()      # every pdf entry still positive
 
 
-def script_weights_update_sequences():
-    rng = np.random.default_rng(7)
-    ops = []
-    for k in range(30000):
-        if k % 5000 == 0:
-            ops.append((6, 0, 0, 0))
-        mode = (k // 5000) % 3
-        if mode == 0:
-            p0, p1, pm = (int(v) for v in rng.integers(1, 32767, size=3))
-        elif mode == 1:                                    # one model much better than the other: drives the weights to the 2^24 normalisation
-            p0, p1 = int(rng.integers(20000, 32767)), int(rng.integers(1, 300)); pm = int(rng.integers(1000, 30000))
-        else:
-            p0 = p1 = pm = int(rng.integers(1, 32767))
-        ops.append((5, p0, p1, pm))
-    return ops
-
-
 @pytest.mark.parametrize("impl", IMPLS)
 def test_weights_update_sequences(codec, impl):
-    run_both(codec, impl, script_weights_update_sequences())
+    run_both(codec, impl, sw.script_weights_update_sequences())
 
 
 def test_what_an_implementation_lacks_is_refused(codec):

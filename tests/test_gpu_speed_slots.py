@@ -11,9 +11,9 @@ the bucketed pass stays in use, the second-generation decoder stays in use and t
 import numpy as np
 import pytest
 
+import gpu_harness as gh
 import pyoracle as po
 import speed_slot_cases as ss
-from test_gpu_bucketed_segments import _assert_same, _encode, _oracle, _split, _tensors
 
 pytestmark = pytest.mark.gpu
 # workgroups of the streaming kernels and decoders: 32 resident groups hold the twelve streams of a batch, one each as under the default
@@ -37,7 +37,7 @@ def _refs(key, r, data):
         o0 = ss.block_type_0(po, o)
         streams = ss.batch(case.fam, data)
         plain = [po.lit_encode(o0, lit) if lit.size else np.zeros(0, np.uint8) for _, lit, _ in streams]
-        _REFS[(key, r)] = (case, g, o0, streams, _oracle(o, streams), plain)
+        _REFS[(key, r)] = (case, g, o0, streams, gh.oracle_bytes(o, streams), plain)
     return _REFS[(key, r)]
 
 
@@ -63,7 +63,7 @@ def _encode_plain(torch, codec, tin, o0, streams, ref, what, path):
     codec.encode_batch(tin["lit"], tin["n"], tin["longest"], outs, in_offsets=tin["off"], in_sizes=tin["sz"])
     st, ran = codec.status(), codec.last_encode_path()
     assert st == 0 and ran == path, (what, st, ran)
-    for i, (a, b) in enumerate(zip(_split(tin, outs), ref)):
+    for i, (a, b) in enumerate(zip(gh.split_outputs(outs, tin["n"]), ref)):
         if a.size != b.size or (a != b).any():
             pytest.fail(f"{what}: stream {i} ({streams[i][0]}, {streams[i][1].size} bytes) differs from the oracle; "
                         + _first_differing_nibble(torch, codec, tin, o0, streams, i))
@@ -91,7 +91,7 @@ def _assert_back(back, buf, tin, streams, what):
 
 def _code_and_decode(torch, da, case, g, o0, streams, coded, plain, decode=True):
     """the whole of one codec's work: lists under path 2 and 1, no lists under path 2 and 1, every decoder on both"""
-    tin = _tensors(torch, streams)
+    tin = gh.ragged_tensors(torch, streams)
     buf = tin["lit"].cpu().numpy()
     assert tin["longest"] == ss.LONG
     codec = da.LiteralCodec(g, tin["longest"])
@@ -102,9 +102,9 @@ def _code_and_decode(torch, da, case, g, o0, streams, coded, plain, decode=True)
     for ask, ran in paths:
         codec.set_encode_path(ask)
         outs = codec.alloc_encode_outputs(tin["n"])
-        st, got, path = _encode(codec, tin, outs)
+        st, got, path = gh.encode_segments(codec, tin, outs)
         assert st == 0 and path == ran, (f"lists, path {ask}", st, path)
-        _assert_same(got, coded, streams, f"lists, path {ask}")
+        gh.assert_same(got, coded, streams, f"lists, path {ask}")
     for gen in _generations(da, codec) if decode else ():
         back = torch.zeros_like(tin["lit"])
         codec.decode_segments_batch(outs["out"], outs["offsets"], outs["sizes"], tin["n"], tin["longest"], tin["sb"], tin["segs"], back, tin["off"], tin["sz"])

@@ -8,13 +8,12 @@ import numpy as np
 import pytest
 
 import bucketed_segment_cases as bc
+import gpu_harness as gh
 import pyoracle as po
 import segment_cases as sc
 import stride_bucketed_cases as stc
-from test_gpu_bucketed_segments import _assert_same, _encode, _oracle, _split, _tensors
 
 pytestmark = pytest.mark.gpu
-BAD_SEGMENT = 4
 KEYS = list(stc.FAMILIES)
 _PLAIN, _LISTS = {}, {}
 
@@ -41,20 +40,8 @@ def _lists(key, sources):
         fam = stc.FAMILIES[key]
         g, o = fam.pair(da, po)
         batches = stc.list_batches(fam, sources)
-        _LISTS[key] = (fam, g, o, batches, {name: _oracle(o, streams) for name, streams in batches.items()})
+        _LISTS[key] = (fam, g, o, batches, {name: gh.oracle_bytes(o, streams) for name, streams in batches.items()})
     return _LISTS[key]
-
-
-def _codec(da, fam, g, longest):
-    codec = da.LiteralCodec(g, max(longest, 16))
-    codec.set_block_types(fam.n_btypes)
-    return codec
-
-
-def _same(got, ref, what):
-    assert len(got) == len(ref)
-    for i, (a, b) in enumerate(zip(got, ref)):
-        assert a.size == b.size and (a == b).all(), f"{what}: stream {i} ({b.size} coded bytes) differs from the oracle"
 
 
 @pytest.mark.parametrize("key", KEYS)
@@ -85,7 +72,7 @@ def test_stride_pass_without_a_list(key, sources):
             codec.set_bucket_batch(sub)
         codec.encode_batch(d_buf, n, longest, outs, in_offsets=d_off, in_sizes=d_sz)
         assert codec.status() == 0 and codec.last_encode_path() == stc.BUCKETED_PATH, what
-        _same(_split(dict(n=n), outs), coded, f"path 2, {what}")
+        gh.assert_same(gh.split_outputs(outs, n), coded, None, f"path 2, {what}")
     back = torch.zeros_like(d_buf)
     codec.decode_batch(outs["out"], outs["offsets"], outs["sizes"], n, longest, back, out_offsets=d_off, out_sizes=d_sz)
     assert codec.status() == 0
@@ -95,11 +82,11 @@ def test_stride_pass_without_a_list(key, sources):
     codec.set_encode_path(0)
     codec.encode_batch(d_buf, n, longest, outs, in_offsets=d_off, in_sizes=d_sz)
     assert codec.status() == 0 and codec.last_encode_path() == stc.AUTOMATIC_PATH_WITHOUT_A_LIST
-    _same(_split(dict(n=n), outs), coded, "automatic")
+    gh.assert_same(gh.split_outputs(outs, n), coded, None, "automatic")
     codec.set_encode_path(1)
     codec.encode_batch(d_buf, n, longest, outs, in_offsets=d_off, in_sizes=d_sz)
     assert codec.status() == 0 and codec.last_encode_path() == 1
-    _same(_split(dict(n=n), outs), coded, "path 1")
+    gh.assert_same(gh.split_outputs(outs, n), coded, None, "path 1")
     codec.close()
 
 
@@ -112,11 +99,11 @@ def test_stride_pass_through_the_host_entry_point(key, sources):
     rows = [(b, c) for b, c in zip(blocks, coded) if b.size >= L][:6]
     data = np.stack([b[:L] for b, _ in rows])
     ref = [c if b.size == L else po.lit_encode(o, b[:L]) for b, c in rows]
-    codec = _codec(da, fam, g, L)
+    codec = gh.codec_for(da, fam, g, L)
     codec.set_encode_path(2)
     packed, offs, sizes = codec.encode_host(data, L)
     assert codec.status() == 0 and codec.last_encode_path() == stc.BUCKETED_PATH
-    _same([packed[int(a):int(a) + int(s)] for a, s in zip(offs, sizes)], ref, "encode_host")
+    gh.assert_same([packed[int(a):int(a) + int(s)] for a, s in zip(offs, sizes)], ref, None, "encode_host")
     back = codec.decode_host(packed, offs, sizes, L)
     assert (np.asarray(back).reshape(len(rows), L) == data).all()
     codec.close()
@@ -129,27 +116,22 @@ def test_stride_pass_codes_segment_lists_bit_exact(key, batch, sources):
     import divans_amd as da
     fam, g, o, batches, coded = _lists(key, sources)
     streams, ref = batches[batch], coded[batch]
-    tin = _tensors(torch, streams)
-    codec = _codec(da, fam, g, tin["longest"])
+    tin = gh.ragged_tensors(torch, streams)
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     assert codec.bucket_stride() == stc.EXPECTED_DISTANCE[key]
     codec.set_encode_path(2)
     outs = codec.alloc_encode_outputs(tin["n"])
     for what, sub in (("one launch sequence", None), ("launch sequences of 9 streams", 9)):
         if sub:
             codec.set_bucket_batch(sub)
-        st, got, path = _encode(codec, tin, outs)
+        st, got, path = gh.encode_segments(codec, tin, outs)
         assert st == 0 and path == stc.BUCKETED_PATH, (what, st, path)
-        _assert_same(got, ref, streams, what)
-    back = torch.zeros_like(tin["lit"])
-    codec.decode_segments_batch(outs["out"], outs["offsets"], outs["sizes"], tin["n"], tin["longest"], tin["sb"], tin["segs"], back, tin["off"], tin["sz"])
-    assert codec.status() == 0
-    back = back.cpu().numpy()
-    for (nm, lit, _), off in zip(streams, tin["offs"]):
-        assert (back[int(off):int(off) + lit.size] == lit).all(), (key, batch, nm)
+        gh.assert_same(got, ref, streams, what)
+    gh.assert_round_trip_segments(torch, codec, tin, outs, streams, f"{key}, {batch}")
     codec.set_encode_path(0)          # automatic: a list stays on the streaming kernels
-    st, got, path = _encode(codec, tin, outs)
+    st, got, path = gh.encode_segments(codec, tin, outs)
     assert st == 0 and path == 1, (st, path)
-    _assert_same(got, ref, streams, "automatic, with a list")
+    gh.assert_same(got, ref, streams, "automatic, with a list")
     codec.close()
 
 
@@ -210,14 +192,14 @@ def test_faulty_lists_are_reported_by_the_stride_pass(key, sources):
     bad, which = sc.bad_lists(streams)
     cases = [("all three", bad, which), ("empty stream, list of 5 bytes", bc.empty_stream_with_bytes_in_its_list(good, 4), (4,)),
              ("block type outside the tables", bc.bad_btype(good, 7, fam.n_btypes), (7,))]
-    tins = [_tensors(torch, b) for _, b, _ in cases]
-    codec = _codec(da, fam, g, max(t["longest"] for t in tins))
+    tins = [gh.ragged_tensors(torch, b) for _, b, _ in cases]
+    codec = gh.codec_for(da, fam, g, max(t["longest"] for t in tins))
     codec.set_encode_path(2)
     for (what, b, skip), tin in zip(cases, tins):
-        st, got, path = _encode(codec, tin)
-        assert st & BAD_SEGMENT and path == stc.BUCKETED_PATH, (what, st, path)
-        _assert_same(got, ref, b, what, skip=skip)
-    st, got, path = _encode(codec, _tensors(torch, good))
+        st, got, path = gh.encode_segments(codec, tin)
+        assert st & gh.BAD_SEGMENT and path == stc.BUCKETED_PATH, (what, st, path)
+        gh.assert_same(got, ref, b, what, skip=skip)
+    st, got, path = gh.encode_segments(codec, gh.ragged_tensors(torch, good))
     assert st == 0 and path == stc.BUCKETED_PATH, (st, path)
-    _assert_same(got, ref, good, "the same streams with their lists in order")
+    gh.assert_same(got, ref, good, "the same streams with their lists in order")
     codec.close()

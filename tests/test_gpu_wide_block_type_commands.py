@@ -7,12 +7,10 @@ Where the context map is not constant the kernels are the wide instances, spelt 
 import pytest
 
 import command_cases as cc
+import gpu_harness as gh
 import history_cases as hc
 import pyoracle as po
 import wide_block_type_cases as wc
-import test_gpu_command_decode as cd
-import test_gpu_command_encode as ce
-import test_gpu_command_history as ch
 
 pytestmark = pytest.mark.gpu
 _CASES = {}
@@ -29,10 +27,10 @@ def _case(fam, sources, history):
         import divans_amd as da
         g, o = fam.pair(da, po)
         if history:
-            _CASES[fam.name, history] = (g, o) + ch._batch(fam, o, hc.directed(fam, sources, "own"), "own")
+            _CASES[fam.name, history] = (g, o) + gh.history_batch(fam, o, hc.directed(fam, sources, "own"), "own")
         else:
             streams = cc.directed(fam, sources)
-            coded = cd._code(o, streams)
+            coded = gh.oracle_bytes(o, streams)
             _CASES[fam.name, history] = (g, o, streams, coded, cc.layout(streams, coded), None)
     return _CASES[fam.name, history]
 
@@ -40,7 +38,7 @@ def _case(fam, sources, history):
 def _kernel(fam, hist):
     mm = fam.mm if fam.mm >= 0 else -1
     caches = (19 if fam.mix else 17) if fam.cached else 0
-    return f"divans_hip::lit_decode2_cmd_{'hist_' if hist else ''}kernel<{mm}, {cd._b(fam.ctxc)}, {cd._b(fam.mix)}, {caches}{'' if fam.ctxc else ', 1'}>"
+    return f"divans_hip::lit_decode2_cmd_{'hist_' if hist else ''}kernel<{mm}, {gh.tf(fam.ctxc)}, {gh.tf(fam.mix)}, {caches}{'' if fam.ctxc else ', 1'}>"
 
 
 def test_the_directed_lists_walk_every_block_type(sources):
@@ -55,26 +53,22 @@ def test_directed_batch_without_history(fam, sources):
     import torch
     import divans_amd as da
     g, o, streams, coded, lay, _ = _case(fam, sources, False)
-    t = cd._tensors(torch, lay)
-    codec = cd._codec(da, fam, g, lay["lit_longest"])
+    t = gh.to_device(torch, lay)
+    codec = gh.codec_for(da, fam, g, lay["lit_longest"])
     for what, setup in (("2 workgroups", lambda c: c.set_geometry(blocks=2)), ("1 workgroup", lambda c: c.set_geometry(blocks=1)),
                         ("direct-mapped decoder asked for", lambda c: c.set_decoder(2))):
         setup(codec)
-        st, raw, flags, name = cd._decode(torch, codec, lay, t)
+        st, raw, flags, name = gh.decode_commands(torch, codec, lay, t)
         assert st == 0 and name == _kernel(fam, False), (what, st, name)
-        cd._assert_raw(raw, lay, streams, what)
+        gh.assert_raw(raw, lay, streams, what)
         assert not flags.any(), what
     # the encode call from the raw bytes and the lists, path 0: the oracle's bytes, then back through the decoder
-    elay = dict(lay); elay["raw"] = lay["expect"].copy()
-    res = ce._encode(torch, codec, elay, ce._tensors(torch, elay))
+    elay = gh.encode_layout(lay)
+    res = gh.encode_commands(torch, codec, elay, gh.to_device(torch, elay))
     assert res["status"] == 0 and not res["flags"].any() and codec.last_encode_path() == 1, (res["status"], res["flags"].tolist(), codec.last_encode_path())
-    ce._assert_coded(res, streams, coded, "encode, path 0")
-    back = cc.layout(streams, [c.copy() for c in res["coded"]], lit_sizes=res["lit_sz"].tolist())
-    assert (back["expect"] == lay["expect"]).all()
-    st, raw, flags, name = cd._decode(torch, codec, back, cd._tensors(torch, back))
+    gh.assert_coded(res, streams, coded, "encode, path 0")
+    gh.round_trip_commands(torch, codec, streams, res, lay, "path 0")
     codec.close()
-    assert st == 0 and not flags.any(), (st, name)
-    cd._assert_raw(raw, back, streams, "round trip")
 
 
 @pytest.mark.parametrize("fam", wc.FAMILIES, ids=repr)
@@ -82,18 +76,17 @@ def test_directed_batch_with_history(fam, sources):
     import torch
     import divans_amd as da
     g, o, streams, coded, lay, hlay = _case(fam, sources, True)
-    t, ht = ch._tensors(torch, lay), ch._tensors(torch, hlay)
-    codec = ch._codec(da, fam, g, lay["lit_longest"])
+    t, ht = gh.to_device(torch, lay), gh.to_device(torch, hlay)
+    codec = gh.codec_for(da, fam, g, lay["lit_longest"], even=True)
     for blocks in (2, 1):
         codec.set_geometry(blocks=blocks)
-        st, raw, flags, name = ch._decode(torch, codec, lay, t, hlay, ht)
+        st, raw, flags, name = gh.decode_commands(torch, codec, lay, t, hlay, ht)
         assert st == 0 and name == _kernel(fam, True), (blocks, st, name)
-        ch._assert_raw(raw, lay, streams, f"{blocks} workgroups")
+        gh.assert_raw(raw, lay, streams, f"{blocks} workgroups")
         assert not flags.any(), blocks
-    elay = ch._enc_lay(lay)
-    et = ch._tensors(torch, elay)
-    res = ch._encode(torch, codec, elay, et, hlay, ht)
+    elay = gh.encode_layout(lay)
+    res = gh.encode_commands(torch, codec, elay, gh.to_device(torch, elay), hlay, ht)
     assert res["status"] == 0 and not res["flags"].any() and codec.last_encode_path() == 1, (res["status"], res["flags"].tolist(), codec.last_encode_path())
-    ch._assert_coded(res, streams, coded, "encode, path 0")
-    ch._round_trip(torch, codec, streams, res, elay, hlay, ht, "path 0")
+    gh.assert_coded(res, streams, coded, "encode, path 0")
+    gh.round_trip_commands(torch, codec, streams, res, elay, "path 0", hlay, ht)
     codec.close()

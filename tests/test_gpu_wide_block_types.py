@@ -7,12 +7,10 @@ with one trailing template argument, under a constant context one of the instanc
 import numpy as np
 import pytest
 
+import gpu_harness as gh
 import pyoracle as po
 import segment_cases as sc
 import wide_block_type_cases as wc
-from test_gpu_segment_cases import (BAD_SEGMENT, WRAP_CASES, _assert_decoded, _assert_same, _b, _codec, _coded_tensors, _decode, _decoder_chains, _encode,
-                                    _input_tensors, _oracle)
-from test_gpu_segment_cases import _assert_kernel as _assert_fused_kernel
 
 pytestmark = pytest.mark.gpu
 _CASES = {}
@@ -29,20 +27,20 @@ def _case(fam, sources):
         import divans_amd as da
         g, o = fam.pair(da, po)
         streams = sc.shapes(fam, sources)
-        _CASES[fam.name] = (g, o, streams, _oracle(o, streams))
+        _CASES[fam.name] = (g, o, streams, gh.oracle_bytes(o, streams))
     return _CASES[fam.name]
 
 
 def _assert_kernel(fam, what, gen, name):
     if fam.ctxc:        # no kernel reads a context table: the instances of eight types
         assert not name.endswith(", 1>") or name.count(",") == 4, (what, name)
-        return _assert_fused_kernel(fam, what, gen, name)
+        return gh.assert_segment_kernel(fam, what, gen, name)
     mm = fam.mm if fam.mm >= 0 else -1
     if gen == 2:        # lit_decode2_kernel_any<MM, false, MIX, true, caches, 1>: the high-row caches in the 2-way organisation, or none
         caches = (19 if fam.mix else 17) if fam.cached else 0
-        assert name == f"divans_hip::lit_decode2_kernel_any<{mm}, false, {_b(fam.mix)}, true, {caches}, 1>", (what, name)
+        assert name == f"divans_hip::lit_decode2_kernel_any<{mm}, false, {gh.tf(fam.mix)}, true, {caches}, 1>", (what, name)
     else:               # lit_decode_kernel<MM, false, MIX, 0, true, 1>: generation 1 reads the wide layout without a cache
-        assert name == f"divans_hip::lit_decode_kernel<{mm}, false, {_b(fam.mix)}, 0, true, 1>", (what, name)
+        assert name == f"divans_hip::lit_decode_kernel<{mm}, false, {gh.tf(fam.mix)}, 0, true, 1>", (what, name)
 
 
 @pytest.mark.parametrize("fam", wc.FAMILIES, ids=repr)
@@ -51,14 +49,14 @@ def test_encode_bit_exact_vs_oracle(fam, sources):
     import torch
     import divans_amd as da
     g, o, streams, coded = _case(fam, sources)
-    tin = _input_tensors(torch, streams)
-    codec = _codec(da, fam, g, tin["longest"])
+    tin = gh.input_tensors(torch, streams)
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     for what, geometry in (("default", None), ("no cache", dict(cache_rows=0)), ("no cache, 1 workgroup", dict(blocks=1))):
         if geometry:
             codec.set_geometry(**geometry)
-        st, got = _encode(torch, codec, tin)
+        st, got, _ = gh.encode_segments(codec, tin, fit=True)
         assert st == 0 and codec.last_encode_path() == 1, (what, st, codec.last_encode_path())      # path 0 codes a list with the streaming kernels
-        _assert_same(got, coded, streams, what)
+        gh.assert_same(got, coded, streams, what)
     codec.close()
 
 
@@ -69,8 +67,8 @@ def test_constant_context_under_the_bucketed_path(fam, sources):
     import torch
     import divans_amd as da
     g, o, streams, coded = _case(fam, sources)
-    tin = _input_tensors(torch, streams)
-    codec = _codec(da, fam, g, tin["longest"])
+    tin = gh.input_tensors(torch, streams)
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     eight = da.LiteralCodec(g, max(tin["longest"], 16)); eight.set_block_types(8)
     if fam.mix:
         for c in (eight, codec):
@@ -79,9 +77,9 @@ def test_constant_context_under_the_bucketed_path(fam, sources):
     else:
         eight.set_encode_path(2)
         codec.set_encode_path(2)
-        st, got = _encode(torch, codec, tin)
+        st, got, _ = gh.encode_segments(codec, tin, fit=True)
         assert st == 0 and codec.last_encode_path() == 2, (st, codec.last_encode_path())
-        _assert_same(got, coded, streams, "path 2")
+        gh.assert_same(got, coded, streams, "path 2")
     eight.close(); codec.close()
 
 
@@ -92,16 +90,16 @@ def test_decode_oracle_bytes_on_every_generation(fam, sources):
     import torch
     import divans_amd as da
     g, o, streams, coded = _case(fam, sources)
-    tin = _input_tensors(torch, streams)
-    tcoded = _coded_tensors(torch, coded)
-    for chain in _decoder_chains(da, fam):
-        codec = _codec(da, fam, g, tin["longest"])
+    tin = gh.input_tensors(torch, streams)
+    tcoded = gh.coded_tensors(torch, coded)
+    for chain in gh.decoder_chains(da, fam):
+        codec = gh.codec_for(da, fam, g, tin["longest"])
         for what, setup, gen in chain:
             setup(codec)
-            st, back, name = _decode(torch, codec, tin, tcoded)
+            st, back, name = gh.decode_segments(torch, codec, tin, tcoded)
             assert st == 0, (what, st, name)
             _assert_kernel(fam, what, gen, name)
-            _assert_decoded(back, tin, streams, what)
+            gh.assert_decoded(back, tin, streams, what)
         codec.close()
 
 
@@ -122,26 +120,26 @@ def test_a_block_type_without_a_table_is_reported(fam, sources):
     g, o, streams, coded = _case(fam, sources)
     few, fcoded, at = streams[:12], coded[:12], 6
     assert few[at][1].size > 16
-    tcoded = _coded_tensors(torch, fcoded)
-    enc = _codec(da, fam, g, max(s[1].size for s in few)); enc.set_geometry(blocks=1)
-    dec = _codec(da, fam, g, max(s[1].size for s in few)); dec.set_geometry(blocks=1)
+    tcoded = gh.coded_tensors(torch, fcoded)
+    enc = gh.codec_for(da, fam, g, max(s[1].size for s in few)); enc.set_geometry(blocks=1)
+    dec = gh.codec_for(da, fam, g, max(s[1].size for s in few)); dec.set_geometry(blocks=1)
     for btype in ((fam.n_btypes,) if fam.n_btypes < 256 else (256, 0xffffffff)):
         batch = _with_bad_type(few, at, btype)
-        tin = _input_tensors(torch, batch)
-        st, got = _encode(torch, enc, tin)
-        assert st & BAD_SEGMENT, (btype, "encode", st)
-        _assert_same(got, fcoded, batch, f"type {btype}", skip=(at,))
-        st, back, name = _decode(torch, dec, tin, tcoded)
-        assert st & BAD_SEGMENT, (btype, "decode", st, name)
+        tin = gh.input_tensors(torch, batch)
+        st, got, _ = gh.encode_segments(enc, tin, fit=True)
+        assert st & gh.BAD_SEGMENT, (btype, "encode", st)
+        gh.assert_same(got, fcoded, batch, f"type {btype}", skip=(at,))
+        st, back, name = gh.decode_segments(torch, dec, tin, tcoded)
+        assert st & gh.BAD_SEGMENT, (btype, "decode", st, name)
         _assert_kernel(fam, f"type {btype}", 2, name)
-        _assert_decoded(back[:tin["total"]], tin, batch, f"type {btype}", skip=(at,))
-    tin = _input_tensors(torch, few)        # ... and the same streams with their lists in order are clean
-    st, got = _encode(torch, enc, tin)
+        gh.assert_decoded(back[:tin["total"]], tin, batch, f"type {btype}", skip=(at,))
+    tin = gh.input_tensors(torch, few)        # ... and the same streams with their lists in order are clean
+    st, got, _ = gh.encode_segments(enc, tin, fit=True)
     assert st == 0
-    _assert_same(got, fcoded, few, "good lists")
-    st, back, name = _decode(torch, dec, tin, tcoded)
+    gh.assert_same(got, fcoded, few, "good lists")
+    st, back, name = gh.decode_segments(torch, dec, tin, tcoded)
     assert st == 0, (st, name)
-    _assert_decoded(back, tin, few, "good lists")
+    gh.assert_decoded(back, tin, few, "good lists")
     enc.close(); dec.close()
 
 
@@ -152,16 +150,16 @@ def test_lists_that_do_not_add_up_are_reported(fam, sources):
     import divans_amd as da
     g, o, streams, coded = _case(fam, sources)
     bad, which = sc.bad_lists(streams)
-    tin = _input_tensors(torch, bad)
-    tcoded = _coded_tensors(torch, coded[:len(bad)])
-    codec = _codec(da, fam, g, tin["longest"])
+    tin = gh.input_tensors(torch, bad)
+    tcoded = gh.coded_tensors(torch, coded[:len(bad)])
+    codec = gh.codec_for(da, fam, g, tin["longest"])
     codec.set_geometry(blocks=2)
-    st, got = _encode(torch, codec, tin)
-    assert st & BAD_SEGMENT, ("encode", st)
-    _assert_same(got, coded, bad, "bad lists", skip=which)
-    st, back, name = _decode(torch, codec, tin, tcoded)
+    st, got, _ = gh.encode_segments(codec, tin, fit=True)
+    assert st & gh.BAD_SEGMENT, ("encode", st)
+    gh.assert_same(got, coded, bad, "bad lists", skip=which)
+    st, back, name = gh.decode_segments(torch, codec, tin, tcoded)
     codec.close()
-    assert st & BAD_SEGMENT, ("decode", st, name)
+    assert st & gh.BAD_SEGMENT, ("decode", st, name)
     _assert_kernel(fam, "bad lists", 2, name)
     offs = tin["off"].cpu().numpy()
     for i, (nm, lit, segs) in enumerate(bad):
@@ -179,22 +177,22 @@ def test_lists_of_low_types_code_alike_under_both_layouts(sources):
     low = wc.low_types_only(streams)
     assert len(low) >= 8 and sum(s[1].size for s in low) > 2000, [s[0] for s in low]
     ref = [coded[i] for i, s in enumerate(streams) if any(s is t for t in low)]
-    tin = _input_tensors(torch, low)
-    tcoded = _coded_tensors(torch, ref)
+    tin = gh.input_tensors(torch, low)
+    tcoded = gh.coded_tensors(torch, ref)
     results = {}
     for n in (9, 8):
         codec = da.LiteralCodec(g, max(tin["longest"], 16))
         codec.set_block_types(n)
-        st, got = _encode(torch, codec, tin)
+        st, got, _ = gh.encode_segments(codec, tin, fit=True)
         assert st == 0, (n, st)
-        st, back, name = _decode(torch, codec, tin, tcoded)
+        st, back, name = gh.decode_segments(torch, codec, tin, tcoded)
         codec.close()
         assert st == 0 and name.count(",") == (5 if n == 9 else 4), (n, st, name)      # a wide instance has a sixth template argument
         results[n] = (got, back)
-    _assert_same(results[9][0], results[8][0], low, "9 types against 8")
-    _assert_same(results[9][0], ref, low, "9 types against the oracle")
+    gh.assert_same(results[9][0], results[8][0], low, "9 types against 8")
+    gh.assert_same(results[9][0], ref, low, "9 types against the oracle")
     assert (results[9][1] == results[8][1]).all()
-    _assert_decoded(results[9][1], tin, low, "9 types")
+    gh.assert_decoded(results[9][1], tin, low, "9 types")
 
 
 def test_a_wrap_checked_speed_runs_the_wide_generation_1_instance(sources):
@@ -202,7 +200,7 @@ def test_a_wrap_checked_speed_runs_the_wide_generation_1_instance(sources):
     cache, whatever was asked for -- the wide lit_decode_kernel instance"""
     import torch
     import divans_amd as da
-    name, speed = WRAP_CASES[0]
+    name, speed = sc.WRAP_CASES[0]
     assert name == "mm4_map_plain"
     fam = wc.by_name("mm4_map_plain_bt256")
     g, o = fam.pair(da, po)
@@ -220,17 +218,17 @@ def test_a_wrap_checked_speed_runs_the_wide_generation_1_instance(sources):
         except RuntimeError:
             pass
     assert len(streams) >= 12 and max(int(s[2]["btype"].max()) for s in streams) >= 128, len(streams)
-    tin = _input_tensors(torch, streams)
-    tcoded = _coded_tensors(torch, coded)
-    codec = _codec(da, fam, g, tin["longest"])
-    st, got = _encode(torch, codec, tin)
+    tin = gh.input_tensors(torch, streams)
+    tcoded = gh.coded_tensors(torch, coded)
+    codec = gh.codec_for(da, fam, g, tin["longest"])
+    st, got, _ = gh.encode_segments(codec, tin, fit=True)
     assert st == 0, st
-    _assert_same(got, coded, streams, "wrap-checked")
-    st, back, kname = _decode(torch, codec, tin, tcoded)
+    gh.assert_same(got, coded, streams, "wrap-checked")
+    st, back, kname = gh.decode_segments(torch, codec, tin, tcoded)
     codec.close()
     assert st == 0, (st, kname)
     assert kname == "divans_hip::lit_decode_kernel<4, false, false, 0, true, 1>", kname
-    _assert_decoded(back, tin, streams, "wrap-checked")
+    gh.assert_decoded(back, tin, streams, "wrap-checked")
 
 
 LATE_WRAP = [f for f in wc.WIDE if f.n_btypes == 256 and f.cached and f.prediction_mode is None]
@@ -248,20 +246,20 @@ def test_every_wide_generation_1_instance_under_a_wrap_checked_speed(fam, source
         for i in range(4):
             cfg.literal_adaptation[i].inc, cfg.literal_adaptation[i].lim = wc.LATE_WRAP_SPEED
     streams = sc.short_streams(fam, sources, 40)
-    coded = _oracle(o, streams)
+    coded = gh.oracle_bytes(o, streams)
     for (_, lit, segs), c in zip(streams, coded):
         assert (po.lit_segments_decode(o, c, lit.size, segs["len"], segs["btype"], segs["last8"]) == lit).all()
-    tin = _input_tensors(torch, streams)
-    tcoded = _coded_tensors(torch, coded)
-    codec = _codec(da, fam, g, tin["longest"])
-    st, got = _encode(torch, codec, tin)
+    tin = gh.input_tensors(torch, streams)
+    tcoded = gh.coded_tensors(torch, coded)
+    codec = gh.codec_for(da, fam, g, tin["longest"])
+    st, got, _ = gh.encode_segments(codec, tin, fit=True)
     assert st == 0, st
-    _assert_same(got, coded, streams, "late wrap")
-    st, back, kname = _decode(torch, codec, tin, tcoded)
+    gh.assert_same(got, coded, streams, "late wrap")
+    st, back, kname = gh.decode_segments(torch, codec, tin, tcoded)
     codec.close()
     assert st == 0, (st, kname)
     _assert_kernel(fam, "late wrap", 1, kname)
-    _assert_decoded(back, tin, streams, "late wrap")
+    gh.assert_decoded(back, tin, streams, "late wrap")
 
 
 def test_what_a_wide_codec_refuses(sources):

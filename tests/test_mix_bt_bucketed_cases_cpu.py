@@ -13,7 +13,7 @@ import ctx_bucketed_cases as cc
 import mix_bt_bucketed_cases as mc
 import pyoracle as po
 import segment_cases as sc
-from test_segment_cases_cpu import rr_segments_decode, rr_segments_encode
+from ref_restatement import rr_segments_decode, rr_segments_encode
 
 KEYS = list(mc.FAMILIES)
 

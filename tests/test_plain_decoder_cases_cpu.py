@@ -9,7 +9,7 @@ import plain_decoder_cases as pc
 import pyoracle as po
 import ref_restatement as rr
 import segment_cases as sc
-from test_segment_cases_cpu import to_rr
+from ref_restatement import to_rr
 
 _BATCHES = {}
 

@@ -78,7 +78,7 @@ def test_oracle_matches_the_reference_build(path, shuffle384):
 @pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f) for f in FILES])
 def test_gpu_matches_the_reference_build(path, shuffle384):
     import divans_amd as da
-    from test_gpu_ffi import ffi_decompress
+    import ffi_harness as fh
     data, cmds, o, pm, keep = _case(path, shuffle384)
     ref = np.fromfile(path, dtype=np.uint8)
     _, lit = _demux(ref)
@@ -88,7 +88,7 @@ def test_gpu_matches_the_reference_build(path, shuffle384):
     packed, offs, sizes = codec.encode_host(data, data.size)
     assert int(sizes[0]) == lit.size and (packed[:lit.size] == lit).all(), "the HIP kernels' LIT stream differs from the reference build's"
     codec.close()
-    assert (ffi_decompress(ref, data.size) == data).all()
+    assert (fh.ffi_decompress(fh.product_library(), ref, data.size) == data).all()
 
 
 # ------------------------------------------------------------------ part 1: wasm/wasm.html:98-107

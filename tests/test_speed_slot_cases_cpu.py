@@ -14,7 +14,7 @@ import pytest
 
 import pyoracle as po
 import speed_slot_cases as ss
-from test_segment_cases_cpu import rr_segments_decode, rr_segments_encode
+from ref_restatement import rr_segments_decode, rr_segments_encode
 
 ROT = range(len(ss.ROTATIONS))
 

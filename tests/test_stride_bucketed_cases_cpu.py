@@ -10,7 +10,7 @@ import pyoracle as po
 import ref_restatement as rr
 import segment_cases as sc
 import stride_bucketed_cases as stc
-from test_segment_cases_cpu import rr_segments_decode, rr_segments_encode, to_rr
+from ref_restatement import rr_segments_decode, rr_segments_encode, to_rr
 
 KEYS = list(stc.FAMILIES)
 

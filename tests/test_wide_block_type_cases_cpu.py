@@ -9,7 +9,7 @@ import pytest
 import pyoracle as po
 import segment_cases as sc
 import wide_block_type_cases as wc
-from test_segment_cases_cpu import rr_segments_decode, rr_segments_encode
+from ref_restatement import rr_segments_decode, rr_segments_encode
 
 
 @pytest.fixture(scope="module")
