@@ -49,6 +49,10 @@ namespace divans_hip {
 namespace {
 
 // LDS is addressed with 32-bit byte addresses (address space 3): no generic-pointer arithmetic in the byte loop
+#ifdef DIVANS_HOST_SIMT      // the stand-in's accessors index the workgroup's LDS array and check the address
+using ::simt::lds_read8; using ::simt::lds_read16; using ::simt::lds_read32; using ::simt::lds_write16; using ::simt::lds_write32;
+__device__ __forceinline__ uint32_t lds_address_of(const uint8_t* lds) { return ::simt::lds_addr(lds); }
+#else
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
@@ -57,6 +61,8 @@ __device__ __forceinline__ void lds_write16(uint32_t a, uint32_t v) { *(lds_u16*
 __device__ __forceinline__ uint32_t lds_read8(uint32_t a) { return *(const lds_u8*)(uintptr_t)a; }
 __device__ __forceinline__ uint32_t lds_read32(uint32_t a) { return *(const lds_u32*)(uintptr_t)a; }
 __device__ __forceinline__ void lds_write32(uint32_t a, uint32_t v) { *(lds_u32*)(uintptr_t)a = v; }
+__device__ __forceinline__ uint32_t lds_address_of(const uint8_t* lds) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds; }
+#endif
 
 constexpr uint32_t kRingWords = 32u;
 constexpr uint32_t kRingBytes = kRingWords * 4u;
@@ -97,9 +103,13 @@ struct Table2 {
     // These loads therefore go out through inline asm (the compiler does not see them), the lookup reports the miss, and the
     // byte loop waits (wait_async) only when some stream of the wave did miss.
     __device__ __forceinline__ int gload_async(uint32_t row) const {
+#ifdef DIVANS_HOST_SIMT
+        return gload(row);
+#else
         int v;
         asm volatile("buffer_load_ushort %0, %1, %2, 0 offen" : "=v"(v) : "v"(lane_off + (row << 5)), "s"(rsrc) : "memory");
         return v;
+#endif
     }
     // Every access of the coder is a read-modify-write of a whole row: a cached row is always dirty, a miss writes the
     // victim's row back (its data is in what the speculative read returned) and fetches the new one.
@@ -165,6 +175,11 @@ struct Table2 {
 };
 
 // wait for the gload_async() requests; the value operands tie the first uses of the loaded registers to this point
+#ifdef DIVANS_HOST_SIMT      // gload_async has returned its value: nothing to wait for, nothing to pad
+__device__ __forceinline__ void wait_async(int&) {}
+__device__ __forceinline__ void wait_async(int&, int&) {}
+template <int N> __device__ __forceinline__ void pad_valu(int&) {}
+#else
 __device__ __forceinline__ void wait_async(int& a) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(a) : : "memory"); }
 __device__ __forceinline__ void wait_async(int& a, int& b) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b) : : "memory"); }
 
@@ -172,6 +187,7 @@ template <int N>
 __device__ __forceinline__ void pad_valu(int& x) {
     if constexpr (N > 0) { asm volatile("v_lshlrev_b32 %0, 1, %0" : "+v"(x)); pad_valu<N - 1>(x); }
 }
+#endif
 
 struct Caches { DmCache hs, hc, ls, lc; };   // high stride rows, high context-map rows (FirstNibble), low stride rows, low context-map rows
 // which of them exist is a compile-time mask CM (an absent cache then costs no registers): bit 0 hs, 1 hc, 2 ls, 3 lc
@@ -313,7 +329,9 @@ __device__ __forceinline__ void advance_state(uint64_t& S, uint32_t slot, uint32
 // frequentist_cdf.rs:74-85 with the search predicate as the increment mask and the row's previous total at hand
 __device__ __forceinline__ int blend2(int c, int li1, bool above, int inc, int lim, int old_max) {
     int c2 = c + inc;
+#ifndef DIVANS_HOST_SIMT
     asm("" : "+v"(c2));                    // one add and one select (not a select of the increment followed by the add)
+#endif
     c = above ? c2 : c;
     const bool renorm = old_max >= lim - inc;       // lim - inc is uniform: a scalar subtraction
     if (__builtin_expect(__ballot(renorm) != 0ull, 0)) {
@@ -477,7 +495,7 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, co
         tb.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)ubase, 0, __builtin_amdgcn_readfirstlane((int)((LIT_THREADS / 16) * slab)), 0x00020000);
         tb.lane_off = (threadIdx.x >> 4) * slab + 2u * (uint32_t)li;
     }
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
+    const uint32_t lds_base = lds_address_of(lds);
     constexpr bool PERM = DIVANS_D2_PERM && MM == 4;
     const uint32_t perm_off = lds_base + (uint32_t)(lv.mix - lv.base);   // behind the configuration tables (lit_lds_bytes2; MM >= 0: no mixing mask there)
     if (PERM) {     // LitBatch::byte_rank: the ranks the codec learned from its data (or was given), or the bytes themselves
@@ -614,26 +632,26 @@ __device__ __forceinline__ void decode2_body(const LitBatch& b, uint8_t* lds, co
 // mixing value is a compile-time constant are held to 72 VGPRs (the mixing ones then park one 64-bit value per stream in
 // scratch, outside the byte loop); the table-driven ones keep what they need.
 template <int MM, bool CTXC, bool MIX, bool SEG, int CM>
-__global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(7))) void lit_decode2_kernel_w7(const LitBatch b) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+__global__ __launch_bounds__(LIT_THREADS) DIVANS_WAVES_PER_EU(7) void lit_decode2_kernel_w7(const LitBatch b) {
+    DIVANS_DYNAMIC_LDS(lds);
     decode2_body<MM, CTXC, MIX, SEG ? LIST_SEGS : LIST_NONE, CM>(b, lds, LitCommandLists{});
 }
 template <int MM, bool CTXC, bool MIX, bool SEG, int CM>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_kernel_any(const LitBatch b) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    DIVANS_DYNAMIC_LDS(lds);
     decode2_body<MM, CTXC, MIX, SEG ? LIST_SEGS : LIST_NONE, CM>(b, lds, LitCommandLists{});
 }
 // The command-list instances (LIST_CMDS), kernels of their own so that the ones above keep their names and their code.  They carry
 // the cursor's state on top of the byte loop's and are left to the register count the compiler gives them.
 template <int MM, bool CTXC, bool MIX, int CM>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_kernel(const LitBatch b, const LitCommandLists cl) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    DIVANS_DYNAMIC_LDS(lds);
     decode2_body<MM, CTXC, MIX, LIST_CMDS, CM>(b, lds, cl);
 }
 // ... and the instances for streams with history (divans_gpu_lit_decode_commands_history_batch): a call without history runs the ones above
 template <int MM, bool CTXC, bool MIX, int CM>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_hist_kernel(const LitBatch b, const LitCommandLists cl) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    DIVANS_DYNAMIC_LDS(lds);
     decode2_body<MM, CTXC, MIX, LIST_CMDS_HIST, CM>(b, lds, cl);
 }
 // The instances of the wide context-table layout: overloads with one trailing template argument (WIDE = 1), so that every instance
@@ -642,19 +660,19 @@ __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_hist_kernel(const
 template <int MM, bool CTXC, bool MIX, bool SEG, int CM, int WIDE>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_kernel_any(const LitBatch b) {
     static_assert(WIDE == 1 && SEG, "the wide instances take segment lists");
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    DIVANS_DYNAMIC_LDS(lds);
     decode2_body<MM, CTXC, MIX, LIST_SEGS, CM, true>(b, lds, LitCommandLists{});
 }
 template <int MM, bool CTXC, bool MIX, int CM, int WIDE>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_kernel(const LitBatch b, const LitCommandLists cl) {
     static_assert(WIDE == 1, "the trailing argument only names the wide layout");
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    DIVANS_DYNAMIC_LDS(lds);
     decode2_body<MM, CTXC, MIX, LIST_CMDS, CM, true>(b, lds, cl);
 }
 template <int MM, bool CTXC, bool MIX, int CM, int WIDE>
 __global__ __launch_bounds__(LIT_THREADS) void lit_decode2_cmd_hist_kernel(const LitBatch b, const LitCommandLists cl) {
     static_assert(WIDE == 1, "the trailing argument only names the wide layout");
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    DIVANS_DYNAMIC_LDS(lds);
     decode2_body<MM, CTXC, MIX, LIST_CMDS_HIST, CM, true>(b, lds, cl);
 }
 
@@ -766,7 +784,7 @@ __device__ __forceinline__ void replay_body(const LitBatch& b, uint8_t* lds) {
         tb.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)ubase, 0, __builtin_amdgcn_readfirstlane((int)((LIT_THREADS / 16) * slab)), 0x00020000);
         tb.lane_off = (threadIdx.x >> 4) * slab + 2u * (uint32_t)li;
     }
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
+    const uint32_t lds_base = lds_address_of(lds);
     constexpr bool PERM = DIVANS_D2_PERM != 0;
     const uint32_t perm_off = lds_base + (uint32_t)(lv.mix - lv.base);
     if (PERM) {
@@ -839,15 +857,15 @@ __device__ __forceinline__ void replay_body(const LitBatch& b, uint8_t* lds) {
 }
 
 template <bool CTXC, bool MIX, int CM>
-__global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(7))) void row_replay_kernel(const LitBatch b) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+__global__ __launch_bounds__(LIT_THREADS) DIVANS_WAVES_PER_EU(7) void row_replay_kernel(const LitBatch b) {
+    DIVANS_DYNAMIC_LDS(lds);
     replay_body<CTXC, MIX, CM>(b, lds);
 }
 
 // one workgroup: histogram of a sample of the batch in LDS, then every thread ranks its own byte value
 __global__ __launch_bounds__(256) void learn_byte_rank_kernel(const uint8_t* data, const uint64_t* offsets, const uint32_t* sizes, uint32_t n_streams,
                                                               uint32_t stream_len, uint32_t sample_streams, uint32_t sample_len, uint8_t* rank) {
-    __shared__ uint32_t cnt[256];
+    DIVANS_STATIC_LDS(uint32_t, cnt, 256);
     cnt[threadIdx.x] = 0u;
     __syncthreads();
     for (uint32_t j = 0; j < sample_streams; ++j) {

@@ -6,6 +6,19 @@
 
 #include "lit_kernels.h"
 
+// DIVANS_HOST_SIMT: a host compiler is building the kernels for the CPU against the lane-lockstep stand-in of tests/c/simt (the
+// device-code tier, tests/c/README.md).  The one switch for everything a host compiler cannot take: inline assembly, LDS address
+// space 3, __shared__ storage, target attributes.  Each spot keeps its device text under #else, so the gfx950 code does not change.
+#ifdef DIVANS_HOST_SIMT
+#define DIVANS_DYNAMIC_LDS(name) uint8_t* const name = ::simt::dynamic_lds()
+#define DIVANS_STATIC_LDS(type, name, n) type* const name = (type*)::simt::static_lds(__FILE__, __LINE__, sizeof(type) * (n))
+#define DIVANS_WAVES_PER_EU(n)
+#else
+#define DIVANS_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) uint8_t name[]
+#define DIVANS_STATIC_LDS(type, name, n) __shared__ type name[n]
+#define DIVANS_WAVES_PER_EU(n) __attribute__((amdgpu_waves_per_eu(n)))
+#endif
+
 namespace divans_hip {
 
 #define DPP_ROW_SHR1 0x111
@@ -263,7 +276,9 @@ struct SegCursor {
 // a workgroup's waves share the CU's L1, which the stores write through): what init_table2 puts between its fill and the row loads.
 __device__ __forceinline__ void drain_stores() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+#ifndef DIVANS_HOST_SIMT
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
 }
 
 // Walks a stream's command list (general streams decoded from their commands: divans_gpu_lit_decode_commands_batch) and EXECUTES it:

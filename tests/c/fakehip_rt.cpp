@@ -20,6 +20,13 @@
 
 #include "../../divans_amd/csrc/lit_kernels.h"
 
+#if defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#include <sanitizer/asan_interface.h>
+#define FAKEHIP_ASAN 1
+#endif
+#endif
+
 using namespace divans_hip;
 
 namespace {
@@ -29,6 +36,8 @@ constexpr size_t kLdsPerCu = 160u * 1024u;      // MI355X
 constexpr int kNumCus = 256;
 constexpr size_t kGranularity = (size_t)2 << 20;
 constexpr size_t kCopyLimit = (size_t)64 << 20;   // larger device-to-device copies are checked, not carried out
+constexpr size_t kFillLimit = (size_t)64 << 20;   // set_fresh_fill: what is filled of a fresh block or mapped chunk, from its start (the rest stays lazily committed zero pages)
+int g_fresh_fill = -1;
 
 struct Mapping { size_t off, bytes; uint64_t handle; bool access; };
 struct Range {
@@ -234,6 +243,19 @@ void complete_stream(void* s, uint64_t upto) { complete_where([&](const Op& p) {
 void complete_legacy() { complete_where([&](const Op& p) { return stream_state(p.stream).kind != fakehip::STREAM_NON_BLOCKING; }); }
 void span_of(std::vector<fakehip::Span>& out, const void* p, size_t bytes, bool write);
 
+// Under AddressSanitizer the rest of a block's last page is poisoned: the block is exactly as long as it was asked for (in front of it
+// and behind the page lies nothing, or another mapping's own checked bytes).
+void guard_tail(uintptr_t base, size_t bytes, bool on) {
+#ifdef FAKEHIP_ASAN
+    const size_t rounded = std::max((bytes + kPage - 1) / kPage * kPage, kPage);
+    if (on) ASAN_POISON_MEMORY_REGION((void*)(base + bytes), rounded - bytes);
+    else ASAN_UNPOISON_MEMORY_REGION((void*)base, rounded);
+#else
+    (void)base; (void)bytes; (void)on;
+#endif
+}
+void fresh_fill(uintptr_t base, size_t bytes) { if (g_fresh_fill >= 0) std::memset((void*)base, g_fresh_fill, std::min(bytes, kFillLimit)); }
+
 void* map_pages(size_t bytes, int prot) {
     bytes = (bytes + kPage - 1) / kPage * kPage;
     void* p = mmap(nullptr, std::max(bytes, kPage), prot, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
@@ -251,6 +273,8 @@ hipError_t new_block(void** ptr, size_t bytes, int kind) {
     Range r;
     r.base = (uintptr_t)map_pages(bytes, PROT_READ | PROT_WRITE); r.bytes = bytes; r.kind = kind; r.device = g_device; r.born = ++g_born;
     g_ranges[r.base] = r;
+    fresh_fill(r.base, bytes);
+    guard_tail(r.base, bytes, true);
     *ptr = (void*)r.base;
     return hipSuccess;
 }
@@ -262,6 +286,7 @@ hipError_t free_block(void* p, const char* fn, int kind) {
     Range r = it->second;
     std::string who;
     if (any_in_flight_on(r.born, &who)) fakehip::violation(who, "lifetime", std::string(fn) + " of a range that launch still references (nothing has waited for it)");
+    guard_tail(r.base, r.bytes, false);
     munmap((void*)r.base, std::max((r.bytes + kPage - 1) / kPage * kPage, kPage));
     if (kind != fakehip::KIND_HOST) g_live -= r.bytes;
     r.alive = false;
@@ -483,6 +508,7 @@ void violation(const std::string& kernel, const std::string& field, const std::s
     abort();
 }
 void set_capacity(size_t bytes) { g_capacity = bytes; }
+void set_fresh_fill(int byte) { g_fresh_fill = byte < 0 ? -1 : (byte & 0xff); }
 size_t live_bytes() { return g_live; }
 size_t reserved_bytes() { return g_reserved; }
 size_t peak_live_bytes() { return g_peak; }
@@ -645,8 +671,10 @@ hipError_t hipMemSetAccess(void* p, size_t bytes, const hipMemAccessDesc*, size_
     if (!r || r->kind != fakehip::KIND_RESERVED) return hipErrorInvalidValue;
     const size_t off = (uintptr_t)p - r->base;
     for (Mapping& m : r->maps) if (m.off >= off && m.off + m.bytes <= off + bytes) {
+        const bool fresh = !m.access;
         m.access = true;
         mprotect((void*)(r->base + m.off), m.bytes, PROT_READ | PROT_WRITE);
+        if (fresh) fresh_fill(r->base + m.off, m.bytes);
     }
     r->sealed = true;
     return hipSuccess;

@@ -48,6 +48,9 @@ size_t live_bytes();                         // blocks + physical chunks alive
 size_t reserved_bytes();                     // address ranges reserved (never handed back)
 size_t peak_live_bytes();                    // the most live_bytes() has been since reset_peak(): what was alive AT an allocation, not after a call
 void reset_peak();
+// What a fresh hipMalloc / hipHostMalloc block and a freshly mapped chunk hold: `byte` (its first 64 MiB; -1, the default: zero pages).
+// A result that changes with the byte depends on memory nobody wrote.
+void set_fresh_fill(int byte);
 
 // ---- time --------------------------------------------------------------------------------------------------------------------
 // The next launches whose kernel name contains `match` take ms[0], ms[1], ... milliseconds (hipEventElapsedTime adds up the launches

@@ -122,24 +122,17 @@ def find_hipcc():
     return None, None
 
 
-def build_capi_contract(csrc=None, tag="contract"):
-    """tests/c/_build/capi_contract: divans_amd/csrc/capi.cpp and the six .hip files compiled for the HOST only (hipcc
-    --offload-host-only: the launchers and kernel stubs, no device code), tests/c/fakehip_rt.cpp in place of libamdhip64 and the
-    driver tests/c/capi_contract.cpp (scenarios on the null stream, and streams_* on a caller's non-blocking stream: tests/c/README.md,
-    "The stream model"), everything under -fsanitize=address,undefined.  A stand-alone program: nothing is preloaded.
-    `csrc` selects another copy of the product sources (a copy with a deliberate break, to see a contract check fire)."""
+SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+
+
+def _host_only_objects(hipcc, csrc, tag, sources, harness):
+    """objects of `sources` (files of csrc) and `harness` (files of tests/c) compiled by hipcc for the HOST only, sanitized"""
     from concurrent.futures import ThreadPoolExecutor
-    hipcc, clang = find_hipcc()
-    if not hipcc:
-        raise RuntimeError("hipcc not found")
-    csrc = csrc or os.path.join(ROOT, "divans_amd", "csrc")
-    os.makedirs(OUT, exist_ok=True)
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
-    flags = ["--offload-arch=gfx950", "--offload-host-only", "-x", "hip", "-std=c++17", "-O1", "-g"] + [f for s in san for f in ("-Xarch_host", s)]
+    flags = ["--offload-arch=gfx950", "--offload-host-only", "-x", "hip", "-std=c++17", "-O1", "-g"] + [f for s in SAN for f in ("-Xarch_host", s)]
     headers = [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h")] + [os.path.join(ROOT, "include", "divans_gpu.h"),
                os.path.join(ROOT, "tests", "c", "fakehip_rt.h"), os.path.abspath(__file__)]
-    jobs = [(os.path.join(csrc, s), os.path.join(OUT, f"{tag}_{s}.o")) for s in CAPI_SOURCES]
-    jobs += [(os.path.join(ROOT, "tests", "c", s), os.path.join(OUT, f"{tag}_{s}.o")) for s in ("fakehip_rt.cpp", "capi_contract.cpp")]
+    jobs = [(os.path.join(csrc, s), os.path.join(OUT, f"{tag}_{s}.o")) for s in sources]
+    jobs += [(os.path.join(ROOT, "tests", "c", s), os.path.join(OUT, f"{tag}_{s}.o")) for s in harness]
 
     def compile_one(job):
         src, obj = job
@@ -148,8 +141,11 @@ def build_capi_contract(csrc=None, tag="contract"):
         return obj
 
     with ThreadPoolExecutor(max_workers=min(len(jobs), 8)) as ex:
-        objs = list(ex.map(compile_one, jobs))
-    # every host-only object refers to the device code it would carry as __hip_fatbin_<hash>: data nobody reads here
+        return list(ex.map(compile_one, jobs))
+
+
+def _fatbin_stub(objs, tag):
+    """every host-only object refers to the device code it would carry as __hip_fatbin_<hash>: data nobody reads here"""
     names = subprocess.run(["nm", "-u"] + objs, check=True, capture_output=True, text=True).stdout.split()
     fatbins = sorted({n for n in names if n.startswith("__hip_fatbin_")})
     stub = os.path.join(OUT, tag + "_fatbins.c")
@@ -157,9 +153,60 @@ def build_capi_contract(csrc=None, tag="contract"):
     if not os.path.exists(stub) or open(stub).read() != text:
         with open(stub, "w") as f:
             f.write(text)
+    return stub
+
+
+def build_capi_contract(csrc=None, tag="contract"):
+    """tests/c/_build/capi_contract: divans_amd/csrc/capi.cpp and the six .hip files compiled for the HOST only (hipcc
+    --offload-host-only: the launchers and kernel stubs, no device code), tests/c/fakehip_rt.cpp in place of libamdhip64 and the
+    driver tests/c/capi_contract.cpp (scenarios on the null stream, and streams_* on a caller's non-blocking stream: tests/c/README.md,
+    "The stream model"), everything under -fsanitize=address,undefined.  A stand-alone program: nothing is preloaded.
+    `csrc` selects another copy of the product sources (a copy with a deliberate break, to see a contract check fire)."""
+    hipcc, clang = find_hipcc()
+    if not hipcc:
+        raise RuntimeError("hipcc not found")
+    csrc = csrc or os.path.join(ROOT, "divans_amd", "csrc")
+    os.makedirs(OUT, exist_ok=True)
+    objs = _host_only_objects(hipcc, csrc, tag, CAPI_SOURCES, ("fakehip_rt.cpp", "capi_contract.cpp"))
+    stub = _fatbin_stub(objs, tag)
     exe = os.path.join(OUT, "capi_contract" if tag == "contract" else "capi_contract_" + tag)
     if _newer(exe, objs + [stub]):
-        subprocess.run([clang] + san + ["-g", "-o", exe, "-x", "c", stub, "-x", "none"] + objs + ["-lpthread"], check=True)
+        subprocess.run([clang] + SAN + ["-g", "-o", exe, "-x", "c", stub, "-x", "none"] + objs + ["-lpthread"], check=True)
+    return exe
+
+
+# ---- the device code on the CPU (tests/c/README.md, "Device code on the CPU") -------------------------------------------------------
+SIMT_SOURCES = ["lit_decode2.hip"]        # the files whose KERNELS run on the lane-lockstep stand-in of tests/c/simt; the rest stay host-only
+
+
+def build_device_code(csrc=None, tag="contract"):
+    """tests/c/_build/device_code: as build_capi_contract, but SIMT_SOURCES are compiled as plain C++ by hipcc's clang++ against
+    tests/c/simt/hip/hip_runtime.h (-DDIVANS_HOST_SIMT), so that their launches run the kernels' own source lane by lane on the
+    runtime's memory; the driver is tests/c/device_code.cpp.  Everything under -fsanitize=address,undefined, nothing preloaded.  With
+    the default sources the host-only objects are the ones build_capi_contract makes (same tag).  `csrc`: a copy with a deliberate
+    break, to see a check fire."""
+    hipcc, clang = find_hipcc()
+    if not hipcc:
+        raise RuntimeError("hipcc not found")
+    csrc = csrc or os.path.join(ROOT, "divans_amd", "csrc")
+    os.makedirs(OUT, exist_ok=True)
+    objs = _host_only_objects(hipcc, csrc, tag, [s for s in CAPI_SOURCES if s not in SIMT_SOURCES], ("fakehip_rt.cpp",))
+    stub = _fatbin_stub(objs, tag + "_simt")
+    simt = os.path.join(ROOT, "tests", "c", "simt")
+    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")
+    flags = ["-x", "c++", "-std=c++17", "-O1", "-g", "-DDIVANS_HOST_SIMT", "-D__HIP_PLATFORM_AMD__", "-Wno-unknown-attributes"] + SAN
+    includes = ["-I" + os.path.join(simt), "-I" + rocm_include, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "c")]
+    headers = [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h")] + [os.path.join(simt, "hip", "hip_runtime.h"), os.path.join(simt, "simt_driver.h"),
+               os.path.join(ROOT, "include", "divans_gpu.h"), os.path.join(ROOT, "tests", "c", "fakehip_rt.h"), os.path.abspath(__file__)]
+    jobs = [(os.path.join(csrc, s), os.path.join(OUT, f"{tag}_simt_{s}.o")) for s in SIMT_SOURCES]
+    jobs += [(os.path.join(simt, "simt.cpp"), os.path.join(OUT, "simt_simt.cpp.o")), (os.path.join(ROOT, "tests", "c", "device_code.cpp"), os.path.join(OUT, "simt_device_code.cpp.o"))]
+    for src, obj in jobs:
+        if not os.path.exists(obj) or any(os.path.getmtime(d) > os.path.getmtime(obj) for d in [src] + headers):
+            subprocess.run([clang] + flags + includes + ["-c", src, "-o", obj], check=True)
+        objs.append(obj)
+    exe = os.path.join(OUT, "device_code" if tag == "contract" else "device_code_" + tag)
+    if _newer(exe, objs + [stub]):
+        subprocess.run([clang] + SAN + ["-g", "-rdynamic", "-o", exe, "-x", "c", stub, "-x", "none"] + objs + ["-lpthread", "-ldl"], check=True)
     return exe
 
 
